@@ -14,7 +14,20 @@ its code; under ``torch.distributed.run`` ``--gpus`` must equal ``WORLD_SIZE``. 
 1,048,576 envs with global ids [rank*B, (rank+1)*B) -- weak scaling, no data-path collective
 (envs are independent); barrier + max-over-ranks timing; ``n_gpus`` = the process group's size.
 
-Order: the supplementary measurements (rollout, BASELINE config 2, the past-MALL 8M-env
+A plain run (``bench.py --gpus N --steps K --warmup W``) does only what the headline needs: it sets
+up the batch, runs the W warm-up launches, times the K launches, writes the final state when
+``--dump-outputs DIR`` is given and prints the line (``value``, ``ms_per_step``, ``config``, ``dist``).
+Everything below -- the supplementary measurements, the roofline with its twin-batch kernel time and
+changed fraction, the memory-floor probe, the copy bandwidth, the shard self-checks and the CPU
+baseline -- runs only with ``--full`` and adds its keys to the same line.
+
+``--dump-outputs DIR``: after the timed launches, the state the stepped batch holds (what ``get_state``
+returns to a caller) is written as ``DIR/state.npy`` -- float32 0/1 node values, one row per env of a
+fixed, seeded sample of the rank's envs -- with the rows' global env ids in ``DIR/env_ids.npy``
+(float64). Same arguments, same inputs (seeded Philox), so two builds can be compared row for row.
+At N > 1 every rank writes ``state_rank<r>.npy`` / ``env_ids_rank<r>.npy``.
+
+Order with ``--full``: the supplementary measurements (rollout, BASELINE config 2, the past-MALL 8M-env
 step run, config 5's R6 chunks with their all-gather) run first, the headline's W warm-up and K
 timed launches after them. The per-launch time depends on where the trajectory is: from fair-bit
 initial states about 40 % of envs change their updated bit per launch and are written back,
@@ -28,13 +41,13 @@ the same launch shape and bytes, no compute) is reported beside it (``floor_GBs`
 ``frac_of_floor`` = kernel floor / kernel time); the guide's MALL gather rate stays as a labelled,
 read-only reference. The 8M-env run (256 MiB of state, past the MALL) carries the HBM-bound figure.
 
-Self-checks (any N): ``shard_check`` re-runs sampled global env ids as 2-env batches and compares
+Self-checks (``--full``, any N): ``shard_check`` re-runs sampled global env ids as 2-env batches and compares
 them with the sharded run (Philox keyed by global id: a one-GPU run gives those ids the same
 trajectory), digesting every rank's rows in global-id order; ``dist`` names the process group's
 backend and size and every rank's kernel time; config 5's actions are keyed by global env id.
 
-Prints ONE JSON line (rank 0) with ``roofline`` and ``cpu_baseline`` (the oracle's C
-restatement on host cores, rank 0 at N = 1 only).
+Prints ONE JSON line (rank 0); with ``--full`` it carries ``roofline`` and ``cpu_baseline`` (the
+oracle's C restatement on host cores, rank 0 at N = 1 only).
 """
 
 from __future__ import annotations
@@ -67,6 +80,13 @@ def parse():
     p.add_argument("--network", default="bittner199")
     p.add_argument("--batch", type=int, default=1 << 20, help="envs per GPU")
     p.add_argument("--seed", type=int, default=0x5EED)
+    p.add_argument("--full", action="store_true",
+                   help="also run the supplements, the roofline's runs (twin-batch kernel time, changed fraction, "
+                        "memory floor, copy bandwidth), the shard self-checks and the CPU baseline; the options "
+                        "below that tune or skip those apply with --full only")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write the stepped batch's final state (a fixed, seeded sample of envs, "
+                        "float32 node values) and the sampled global env ids as DIR/<name>.npy")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-seconds", type=float, default=10.0)
     p.add_argument("--rollout", type=int, default=64, help="updates per launch for the supplementary rollout line")
@@ -693,6 +713,81 @@ def guarded(fn, *a):
         return {"error": f"{type(exc).__name__}: {exc}"}
 
 
+def supplements(args, sup, net, B, world, rank, device, dist):
+    """``--full``: the supplementary measurements into ``sup`` (every rank); returns the memory-floor
+    probe (or None) and rank 0's copy bandwidth."""
+    try:
+        valu = json.loads(Path(args.valu_file).read_text()).get("kernels", {})
+    except (OSError, ValueError):
+        valu = {}
+    floor = None
+    if args.probe:
+        try:
+            floor = MemFloor()
+        except OSError:
+            floor = None
+    if args.rollout > 1:
+        sup["rollout"] = guarded(rollout_supplement, net, B, device, args.seed, args.rollout, valu)
+    if args.config2:
+        sup["config2_bittner28"] = guarded(config2_supplement, device)
+    if args.beyond_mall and B == 1 << 20:
+        sup["beyond_mall_8m"] = guarded(beyond_mall_supplement, net, device, args.seed, floor)
+    if args.r6_chunks > 0:
+        sup["config5_r6"] = guarded(r6_supplement, args, world, rank, device, dist, valu)
+    if args.mt and args.network == "bittner199":
+        sup["mt_mode"] = guarded(mt_supplement, net, device)
+    return floor, (guarded(copy_bandwidth, device) if rank == 0 else None)
+
+
+DUMP_SAMPLE_SEED = 0xD0A5EED  # the sampled envs depend on the batch size alone
+DUMP_MAX_ENVS = 65536         # 65,536 envs x 199 nodes x 4 B = 52 MB (the dump stays under 64 MB)
+DUMP_MAX_BYTES = 60_000_000
+
+
+def dump_outputs(out_dir, state, n_nodes, env_base, rank, world):
+    """``--dump-outputs``: the timed batch's final state (``get_state``'s packed words, unpacked to
+    float32 0/1 node values) for a fixed, seeded sample of this rank's envs (all of them when they
+    fit), and the rows' global env ids (float64: exact below 2^53)."""
+    import numpy as np
+
+    from gym_pbn_amd.batch import unpack_bits
+
+    B = state.shape[0]
+    n = max(1, min(B, DUMP_MAX_ENVS, DUMP_MAX_BYTES // (4 * n_nodes + 8)))
+    rows = np.arange(B) if n == B else np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(B, n, replace=False))
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    tag = "" if world == 1 else f"_rank{rank}"
+    np.save(d / f"state{tag}.npy", unpack_bits(state[rows], n_nodes).astype(np.float32))
+    np.save(d / f"env_ids{tag}.npy", (rows + env_base).astype(np.float64))
+
+
+def headline_line(args, net, world, dist, value, elapsed):
+    """The line's fields every run prints: the headline figure and the workload it was measured on."""
+    return {
+        "metric": "env-steps/sec (whole node), Bittner-200, batch=1M; achieved HBM GB/s",
+        "value": value,
+        "unit": "env-steps/s",
+        "n_gpus": dist.get_world_size() if dist is not None else 1,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed * 1e3 / args.steps,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u64",
+        "data": "synthetic (Philox fair-bit initial states; network exported from the reference's "
+                "predictor_sets_200_5_kmeans.pkl)",
+        "config": {
+            "workload": "Bittner-200 async node update (R1 Graph.step), step mode: one update per env per "
+                        "launch, state resident in device memory",
+            "network": args.network, "n_nodes": net.n_nodes, "state_words": net.n_words,
+            "batch_per_gpu": args.batch, "global_batch": world * args.batch, "updates_per_step": 1,
+            "parallelism": f"dp{world} (env shards, no collective)", "rng": "philox4x32-10",
+        },
+    }
+
+
 def main():
     args = parse()
     import atexit
@@ -741,30 +836,10 @@ def main():
         batch.sync()
         return
 
-    try:
-        valu = json.loads(Path(args.valu_file).read_text()).get("kernels", {})
-    except (OSError, ValueError):
-        valu = {}
-    floor = None
-    if args.probe:
-        try:
-            floor = MemFloor()
-        except OSError:
-            floor = None
-
-    # ---- supplements first (every rank, so every GPU enters the headline in the same clock state)
-    sup = {}
-    if args.rollout > 1:
-        sup["rollout"] = guarded(rollout_supplement, net, B, device, args.seed, args.rollout, valu)
-    if args.config2:
-        sup["config2_bittner28"] = guarded(config2_supplement, device)
-    if args.beyond_mall and B == 1 << 20:
-        sup["beyond_mall_8m"] = guarded(beyond_mall_supplement, net, device, args.seed, floor)
-    if args.r6_chunks > 0:
-        sup["config5_r6"] = guarded(r6_supplement, args, world, rank, device, dist, valu)
-    if args.mt and args.network == "bittner199":
-        sup["mt_mode"] = guarded(mt_supplement, net, device)
-    copy = guarded(copy_bandwidth, device) if rank == 0 else None
+    # ---- --full: supplements first (every rank, so every GPU enters the headline in the same clock state)
+    sup, floor, copy = {}, None, None
+    if args.full:
+        floor, copy = supplements(args, sup, net, B, world, rank, device, dist)
 
     # ---- the headline: W warm-up launches, then exactly K timed launches
     def barrier():
@@ -789,8 +864,27 @@ def main():
     t1 = time.perf_counter()
     barrier()
     elapsed = max_over_ranks(t1 - t0, dist, device=_dev(device))
-    final_state = batch.get_state()  # host copy for the shard self-check below (after the window)
+    # host copy (after the window) for --dump-outputs and --full's shard self-check below
+    final_state = batch.get_state() if (args.full or args.dump_outputs) else None
     batch.close()
+    total_steps = world * B * args.steps
+    value = total_steps / elapsed
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, final_state, net.n_nodes, shard.env_base, rank, world)
+    if not args.full:  # the plain run ends here: the headline alone
+        ranks = per_rank({"rank": rank, "elapsed_s": t1 - t0, "device": device}, dist)
+        if rank == 0:
+            print(json.dumps({
+                **headline_line(args, net, world, dist, value, elapsed),
+                "node_updates_per_s": value,
+                "dist": {"backend": dist.get_backend() if dist is not None else None,
+                         "world_size": dist.get_world_size() if dist is not None else 1, "per_rank": ranks},
+                "process_census": process_census()}), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     # kernel time of the same window: a twin batch (same network, seed and env ids: the identical
     # Philox trajectory, so the same envs change and are written back per launch) runs the same W
     # warm-up launches, then the same K launches inside one HIP-event region on its stream
@@ -830,8 +924,6 @@ def main():
     contract_bytes = 16 * W * B  # read + write the packed state of every env
     avg_kernel_s = kernel_ms / 1e3 / max(launches, 1)
     traffic, pmc_src = read_pmc(args.pmc_file, f"{args.network}:{B}")
-    total_steps = world * B * args.steps
-    value = total_steps / elapsed
     if rank == 0:
         alg_bytes = min_bytes(W, B, q)
         achieved = alg_bytes / avg_kernel_s / 1e9 if launches else None
@@ -891,26 +983,7 @@ def main():
             rf["achievable_copy_GBs"] = copy
             rf["achievable_copy_source"] = "torch device-to-device copy of 2 GiB (past the MALL), read + write bytes"
         out = {
-            "metric": "env-steps/sec (whole node), Bittner-200, batch=1M; achieved HBM GB/s",
-            "value": value,
-            "unit": "env-steps/s",
-            "n_gpus": dist.get_world_size() if dist is not None else 1,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed * 1e3 / args.steps,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u64",
-            "data": "synthetic (Philox fair-bit initial states; network exported from the reference's "
-                    "predictor_sets_200_5_kmeans.pkl)",
-            "config": {
-                "workload": "Bittner-200 async node update (R1 Graph.step), step mode: one update per env per "
-                            "launch, state resident in device memory",
-                "network": args.network, "n_nodes": net.n_nodes, "state_words": W,
-                "batch_per_gpu": B, "global_batch": world * B, "updates_per_step": 1,
-                "parallelism": f"dp{world} (env shards, no collective)", "rng": "philox4x32-10",
-            },
+            **headline_line(args, net, world, dist, value, elapsed),
             "roofline": rf,
             "node_updates_per_s": value,
             "dist": {"backend": dist.get_backend() if dist is not None else None,

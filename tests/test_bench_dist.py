@@ -1,5 +1,5 @@
 """bench.py's multi-rank bookkeeping rehearsed on CPU: two gloo ranks run bench.main() end to end --
-headline window, supplements, config 5's three R6 figures with their per-chunk trajectory
+with ``--full``: headline window, supplements, config 5's three R6 figures with their per-chunk trajectory
 all-gathers (rollout.TrajectoryCollector, the real class, on CPU tensors) -- with only the GPU
 work stubbed (a stand-in PBNBatch; bench's device/process-group helpers on CPU). Every collective
 each rank issues is recorded: both ranks must issue the same sequence (a rank that skipped or
@@ -68,7 +68,7 @@ class _FakeNet:
         self.n_nodes, self.n_words, self.name = net.n_nodes, net.n_words, net.name
 
 
-def _worker(rank, world, port, out_dir):
+def _worker(rank, world, port, out_dir, extra):
     os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
                       MASTER_PORT=str(port))
     for p in (ROOT, ROOT / "gym-pbn-stac_amd"):
@@ -106,7 +106,7 @@ def _worker(rank, world, port, out_dir):
     gb.Net = _FakeNet
     gb.EnvConfig = lambda net, atts, horizon=100, **k: ("cfg", len(atts), horizon)
     sys.argv = ["bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "4096", "--r6-batch", "256",
-                "--r6-chunks", "2", "--no-probe", "--dist-backend", "gloo", "--no-cpu-baseline"]
+                "--r6-chunks", "2", "--no-probe", "--dist-backend", "gloo", "--no-cpu-baseline", *extra]
     out = Path(out_dir)
     with open(out / f"stdout{rank}.txt", "w") as fh:
         old, sys.stdout = sys.stdout, fh
@@ -118,7 +118,7 @@ def _worker(rank, world, port, out_dir):
 
 
 def test_two_rank_bench_bookkeeping_on_cpu(tmp_path):
-    mp.spawn(_worker, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
+    mp.spawn(_worker, args=(2, _free_port(), str(tmp_path), ["--full"]), nprocs=2, join=True)
     c0 = json.loads((tmp_path / "calls0.json").read_text())
     c1 = json.loads((tmp_path / "calls1.json").read_text())
     assert c0 == c1  # same collectives, same order, same shapes on both ranks
@@ -148,6 +148,55 @@ def test_two_rank_bench_bookkeeping_on_cpu(tmp_path):
     assert len(r6["chunk_diag"]) == 2 and "slowest_env_updates" in r6["chunk_diag"][0]
     assert "handoffs_last_fused_launch" in r6
     assert "process_census" in d
+
+
+def test_two_rank_plain_run_is_the_headline_alone(tmp_path):
+    """Without ``--full``: the same collectives on both ranks, the headline's fields and nothing that
+    takes a run of its own; ``--dump-outputs`` writes every rank's state sample and env ids."""
+    import numpy as np
+
+    dump = tmp_path / "dump"
+    mp.spawn(_worker, args=(2, _free_port(), str(tmp_path), ["--dump-outputs", str(dump)]), nprocs=2, join=True)
+    c0 = json.loads((tmp_path / "calls0.json").read_text())
+    assert c0 == json.loads((tmp_path / "calls1.json").read_text())
+    names = [c[0] for c in c0]
+    assert "all_gather_into_tensor" not in names and names[-1] == "barrier"  # no config-5 gathers
+    lines = [ln for ln in (tmp_path / "stdout0.txt").read_text().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1 and not (tmp_path / "stdout1.txt").read_text().strip()
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 2 and d["steps"] == 3 and d["warmup"] == 1 and d["config"]["global_batch"] == 2 * 4096
+    assert d["unit"] == "env-steps/s" and d["higher_is_better"] is True and d["dtype"] == "u64"
+    assert d["ms_per_step"] > 0 and abs(d["value"] * d["ms_per_step"] / 1e3 - 2 * 4096) < 1e-6 * 2 * 4096
+    assert [p["rank"] for p in d["dist"]["per_rank"]] == [0, 1]
+    for key in ("roofline", "shard_check", "cpu_baseline", "rollout", "config2_bittner28", "beyond_mall_8m",
+                "config5_r6", "mt_mode"):
+        assert key not in d
+    for r in (0, 1):
+        st, ids = np.load(dump / f"state_rank{r}.npy"), np.load(dump / f"env_ids_rank{r}.npy")
+        assert st.dtype == np.float32 and st.shape == (4096, 199) and ids.dtype == np.float64
+        assert np.array_equal(ids, np.arange(4096) + r * 4096)
+
+
+def test_dump_outputs_samples_a_large_batch_the_same_way_every_time(tmp_path):
+    """A batch past the dump's row cap: a fixed sample of rows (same on every call), unpacked node values."""
+    import numpy as np
+
+    for p in (ROOT, ROOT / "gym-pbn-stac_amd"):
+        sys.path.insert(0, str(p))
+    import bench
+    from gym_pbn_amd.batch import unpack_bits
+
+    B = bench.DUMP_MAX_ENVS + 1000
+    state = np.random.default_rng(1).integers(0, 1 << 63, size=(B, 4), dtype=np.uint64)
+    for name in ("a", "b"):
+        bench.dump_outputs(tmp_path / name, state, 199, 1 << 20, 0, 1)
+    st, ids = np.load(tmp_path / "a" / "state.npy"), np.load(tmp_path / "a" / "env_ids.npy")
+    assert st.shape == (bench.DUMP_MAX_ENVS, 199) and st.dtype == np.float32 and st.nbytes + ids.nbytes <= 64e6
+    assert np.array_equal(st, np.load(tmp_path / "b" / "state.npy"))
+    assert np.array_equal(ids, np.load(tmp_path / "b" / "env_ids.npy"))
+    rows = (ids - (1 << 20)).astype(np.int64)
+    assert np.all(np.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < B
+    assert np.array_equal(st, unpack_bits(state[rows], 199))
 
 
 def test_failed_process_group_exits_nonzero_promptly():

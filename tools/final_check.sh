@@ -15,3 +15,4 @@ step() {
 step gputests 600 python -u -m pytest -x -q --timeout 120 --timeout-method thread -m gpu tests/
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')"
 step bench 300 python bench.py --steps 20 --warmup 5
+step bench_full 600 python bench.py --full --steps 20 --warmup 5

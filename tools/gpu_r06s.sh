@@ -6,5 +6,5 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout
 tail -2 $O/gpu_tests.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 1; }
 tail -1 $O/smoke.log
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $O/bench.out 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > $O/bench.out 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 tail -c 400 $O/bench.out

@@ -16,8 +16,8 @@ run() {
   echo "=== [$label] rc=$rc"; tail -n 3 $O/$label.out
   [ $rc -eq 0 ] || exit $rc
 }
-run bench 300 python bench.py --steps 20 --warmup 5
-run bench_prof 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -o bench -- python3 bench.py --steps 20 --warmup 5
+run bench 300 python bench.py --full --steps 20 --warmup 5
+run bench_prof 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -o bench -- python3 bench.py --full --steps 20 --warmup 5
 run trace_split 60 python tools/trace_split.py $(ls $O/prof_bench/*/bench_kernel_trace.csv $O/prof_bench/bench_kernel_trace.csv 2>/dev/null | head -n 1)
 run r6_lane_131k 200 python tools/r6_group_sweep.py 131072 1
 run r6_lane_1m 200 python tools/r6_group_sweep.py 1048576 1

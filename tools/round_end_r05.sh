@@ -15,8 +15,8 @@ run() {
   echo "=== [$label] rc=$rc"; tail -n 3 $O/$label.out | cut -c1-300
   [ $rc -eq 0 ] || exit $rc
 }
-run bench 300 python bench.py --steps 20 --warmup 5
-run bench_prof 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -o bench -- python3 bench.py --steps 20 --warmup 5
+run bench 300 python bench.py --full --steps 20 --warmup 5
+run bench_prof 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -o bench -- python3 bench.py --full --steps 20 --warmup 5
 run trace_split 60 python tools/trace_split.py $(ls $O/prof_bench/*/bench_kernel_trace.csv $O/prof_bench/bench_kernel_trace.csv 2>/dev/null | head -n 1)
 run valu_pmc 400 python tools/valu_pmc.py
 run pmc_traffic 400 python tools/pmc_traffic.py
