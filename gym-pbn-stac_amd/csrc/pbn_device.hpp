@@ -455,4 +455,12 @@ __device__ __forceinline__ void from_plane(const P_t& P, uint64_t (&s)[W]) {
     for (int k = 0; k < W; ++k) s[k] = (uint64_t)P.get(2 * k) | ((uint64_t)P.get(2 * k + 1) << 32);
 }
 
+// Orders a wave's LDS accesses without a workgroup barrier: writes before it are visible to the
+// wave's other lanes after it (release fence, wave barrier, acquire fence).
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 }  // namespace pbn

@@ -1,568 +1,31 @@
-// pbn_kernels.hip -- gfx950 kernels of the vectorised PBN simulator.
+// pbn_env.hip -- the R6 env-step kernel k_env (lane, cooperative-draw and tail modes) and the env-step
+// dispatch; group mode's kernel k_env_grp is in pbn_env_grp.hip.
 //
-// Mapping: one lane owns one env at a time; its state words are loaded into VGPRs and, for the
-// node update, spread over the lane's column of LDS state planes. Each workgroup stages the
-// network image (thresholds, predictor records or probability tables) into LDS once. Step mode
-// (the bench kernel, k_step<.., 1024>): 1024-thread workgroups, two per CU, every thread owning
-// one pair of envs (e, e + grid stride) at 1M envs (more pairs per thread, grid-stride, above);
-// rollout / R6 / SSD kernels: 256-thread workgroups sized to what is resident, lanes refilled
-// from a work counter (R6) or walking envs in a grid-stride loop.
+// Mapping: one lane owns one env at a time, its state in the lane's column of LDS state planes; each
+// workgroup stages the network image into LDS once; 256-thread workgroups sized to what is resident,
+// lanes refilled from a work counter.
 //
 // Reference semantics implemented (file:line in the reference):
-//   k_step    Graph.step base.py:306-312 (+ Node.Predstep :89-119) and
-//             PBN.step common/pbn.py:129-133 (+ Node.compute_next_value common/node.py:34-38)
-//   k_init    Graph.genRandState base.py:368-370 / PBN.reset(None) pbn.py:105-118 /
-//             PBNTargetMultiEnv.reset pbn_target_multi.py:237-249 (Philox streams)
-//   k_flip    Graph.flipNode base.py:280-284 over a multi-action row (pbn_target_multi.py:120-131)
 //   k_env     PBNTargetMultiEnv.step pbn_target_multi.py:119-154
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "pbn_device.hpp"
+#include "pbn_env_device.hpp"
+#include "pbn_launch.hpp"
 #include "pbn_params.hpp"
 
 namespace pbn {
 
 #ifdef PBN_STAMPS
-// Measurement builds only (tools/build_exp.sh -DPBN_STAMPS): per-wave s_memrealtime stamps (100 MHz)
-// of the step kernel's phases, kept in registers and written once at the end of the wave.
-__device__ uint64_t g_stamps[16384 * 8];
+// Measurement builds only (tools/build_exp.sh -DPBN_STAMPS): per-wave s_memrealtime stamps (100 MHz).
 // k_env (cooperative-draw path): per wave, ENV_STAMPS words (tools/env_stamps.py reads them)
 constexpr int ENV_STAMPS = 40;
 __device__ uint64_t g_env_stamps[16384 * ENV_STAMPS];
 #endif
 
-// ------------------------------------------------------------------ step
-// Layout per workgroup in LDS: [network image][state planes]. The state planes
-// hold, for the env each lane is working on, its 2W dwords in planar order
-// (dword d of lane l at plane d, column l), so reading node i of the own env is
-// one conflict-free ds_read_b32 at plane (i >> 5) and an update is one
-// read-modify-write of one dword -- instead of ~20 VALU selects per bit when the
-// words sit in VGPRs. Columns are lane-private: no barrier is needed around them.
-//
-// Each thread walks envs e0, e0 + stride, ... with the next env's state load in
-// flight while the current env is computed (software pipeline), so HBM traffic
-// of one env overlaps the Philox/LDS work of the previous one.
-//
-// SB (threads per workgroup) trades LDS staging traffic against scheduling
-// granularity: the image is staged once per workgroup, so 1024-thread groups
-// read it from L2 4x less often than 256-thread groups.
-// One update per env (T == 1), Philox. Envs are taken in pairs (e, e + stride); at the
-// bench sizes every thread owns exactly one pair. The pair's draws and (for predictor
-// networks) its predictor records depend only on (seed, update counter, env id), so
-// they are computed while the pair's state loads are in flight.
-template <int W, int KIND, int STORE, int SB, bool PRE = false>
-__device__ __forceinline__ void k_step_single(const StepArgs& a, uint8_t* lds, uint64_t e, uint64_t stride,
-                                              uint64_t (&cur)[W], uint32_t N, uint64_t (*pre_nxt)[W] = nullptr) {
-    // graph replays read the batch's update counter from device memory (k_bump advances it)
-    const uint64_t u = a.update_base + (a.ubase_dev ? *a.ubase_dev : 0ull);
-    const uint64_t po = stride;  // second env of the pair (adjacent envs measured slower: 8.2 vs 7.8 us)
-    uint64_t nxt[W];
-    uint32_t i0 = 0, i1 = 0;
-    uint64_t q0 = 0, q1 = 0;
-    // envs 2m / 2m + 1 share a Philox call (pbn_device.hpp): with an even env base, lane parity is
-    // env parity and the lane pair computes one call per env pair each (step_words_paired). A
-    // partner lane that has left the loop holds envs >= B only, so the words it no longer sends
-    // belong to envs that are not applied.
-    const bool paired = (a.env_base & 1u) == 0u;
-    const bool odd = (threadIdx.x & 1u) != 0u;
-    auto draws = [&](uint64_t ea) {
-        const uint64_t g0 = a.env_base + ea, g1 = g0 + po;
-        uint32_t n0, c0, n1, c1;
-        if (paired) {
-            step_words_paired(a.seed, u, g0, g1, odd, n0, c0, n1, c1);
-        } else {
-            step_words(a.seed, u, g0, n0, c0);
-            step_words(a.seed, u, g1, n1, c1);
-        }
-        i0 = philox_node<KIND>(n0, N);
-        i1 = philox_node<KIND>(n1, N);
-        // predictor mix: the choice word itself (compact image, thresholds on the word); tables: k53
-        q0 = KIND == KIND_PREDICTOR_MIX ? (uint64_t)c0 : u32_k53(c0);
-        q1 = KIND == KIND_PREDICTOR_MIX ? (uint64_t)c1 : u32_k53(c1);
-    };
-#ifdef PBN_STAMPS
-    uint64_t st[8] = {__builtin_amdgcn_s_memrealtime(), 0, 0, 0, 0, 0, 0, 0};
-#endif
-    const Thr32 X = thr32_layout(a.L);
-    if constexpr (PRE) {  // image staged and both loads issued by the caller (k_step)
-#pragma unroll
-        for (int k = 0; k < W; ++k) nxt[k] = (*pre_nxt)[k];
-        draws(e);
-#ifdef PBN_STAMPS
-        st[2] = st[0];  // the caller's barrier was passed on entry here
-        st[1] = __builtin_amdgcn_s_memrealtime();
-#endif
-    } else {
-    if (e + po < a.B) load_state<W>(a.state + (e + po) * W, nxt);
-    draws(e);
-#ifdef PBN_STAMPS
-    st[1] = __builtin_amdgcn_s_memrealtime();
-#endif
-    if constexpr (KIND == KIND_PREDICTOR_MIX)  // the compact image (thresholds on the choice word)
-        stage_image(reinterpret_cast<const uint4*>(reinterpret_cast<const uint8_t*>(a.img) + a.L.bytes), X.bytes / 16,
-                    reinterpret_cast<uint4*>(lds));
-    else
-        stage_image(reinterpret_cast<const uint4*>(a.img), a.L.bytes / 16, reinterpret_cast<uint4*>(lds));
-    __syncthreads();
-    }
-#ifdef PBN_STAMPS
-    st[2] = __builtin_amdgcn_s_memrealtime();
-#endif
-    const PlaneT<SB> P{reinterpret_cast<uint32_t*>(lds + a.L.plane_off) + threadIdx.x};
-    while (e < a.B) {
-        const uint64_t e1 = e + po;
-        uint64_t r0 = 0, r1 = 0;
-        if constexpr (KIND == KIND_PREDICTOR_MIX) {  // state-independent: before the loads land
-            r0 = predictor_record32(i0, (uint32_t)q0, lds, X);
-            r1 = predictor_record32(i1, (uint32_t)q1, lds, X);
-        }
-#ifdef PBN_STAMPS
-        if (!st[3]) {
-            __builtin_amdgcn_s_waitcnt(0);  // records read and state landed (measurement build)
-            st[3] = __builtin_amdgcn_s_memrealtime();
-        }
-#endif
-        if constexpr (STORE == STORE_DIRTY) {
-            // Both envs evaluated first (plane writes and reads of env 1 issued right behind env 0's;
-            // LDS runs a wave's operations in order, so reusing the column needs no wait), then both
-            // stores: with env 0's store issued before env 1's loads were consumed, the compiler
-            // waited for that store to complete (vmcnt(0)) before env 1's plane writes.
-            // Env 1 is evaluated unconditionally (past B: junk from a clamped or skipped load,
-            // never stored).
-            // the plane's last dword holds nodes >= 64W - 32 only: it is written only if N reaches it
-            // (Bittner-200: 7 of the 8 dwords, one LDS write of eight saved per env)
-            const bool last_dw = N > 64u * W - 32u;
-            auto eval = [&](const uint64_t (&s)[W], uint32_t i, uint64_t r, uint64_t q, uint32_t& self) {
-#pragma unroll
-                for (int k = 0; k < W; ++k) {
-                    P.put(2 * k, (uint32_t)s[k]);
-                    if (k + 1 < W || last_dw) P.put(2 * k + 1, (uint32_t)(s[k] >> 32));
-                }
-                self = P.get(i >> 5);
-                if constexpr (KIND == KIND_PREDICTOR_MIX)
-                    return predictor_apply(P, i, self, r);
-                else
-                    return table_eval_lds(P, i, q, lds, a.L);
-            };
-            uint32_t self0, self1;
-            const uint32_t y0 = eval(cur, i0, r0, q0, self0);
-            const uint32_t y1 = eval(nxt, i1, r1, q1, self1);
-            // store the whole env (32 B at W = 4), and only if its bit changed: a full aligned env
-            // write measured faster than writing just the 16-B half that holds node i (7.69 vs
-            // 7.93 us at 1M envs), partial sector writes cost extra. The env's words are still in
-            // registers: bit i is flipped there (one 64-bit select per word) rather than written to
-            // the plane and all 2W dwords read back
-            auto put = [&](const uint64_t (&s)[W], uint64_t eh, uint32_t i) {
-                uint64_t out[W];
-                const uint32_t wi = i >> 6;
-                const uint64_t m = 1ull << (i & 63u);
-#pragma unroll
-                for (int k = 0; k < W; ++k) out[k] = s[k] ^ ((uint32_t)k == wi ? m : 0ull);
-                store_state<W>(a.state + eh * W, out);
-            };
-            if (((self0 >> (i0 & 31u)) & 1u) != y0) put(cur, e, i0);
-            if (e1 < a.B && ((self1 >> (i1 & 31u)) & 1u) != y1) put(nxt, e1, i1);
-        } else {
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const uint64_t eh = h ? e1 : e;
-            if (eh >= a.B) break;
-            uint64_t(&s)[W] = h ? nxt : cur;
-            const uint32_t i = h ? i1 : i0;
-            const uint32_t d = i >> 5, sh = i & 31u;
-            to_plane<W>(P, s);
-            const uint32_t self = P.get(d);
-            uint32_t y;
-            if constexpr (KIND == KIND_PREDICTOR_MIX)
-                y = predictor_apply(P, i, self, h ? r1 : r0);
-            else
-                y = table_eval_lds(P, i, h ? q1 : q0, lds, a.L);
-            const uint32_t nv = (self & ~(1u << sh)) | (y << sh);
-            P.put(d, nv);
-            uint64_t out[W];
-            from_plane<W>(P, out);
-            store_state<W>(a.state + eh * W, out);
-        }
-        }
-#ifdef PBN_STAMPS
-        if (!st[4]) st[4] = __builtin_amdgcn_s_memrealtime();  // the first pair's stores issued
-#endif
-        e += 2 * stride;
-        if (e < a.B) {
-            load_state<W>(a.state + e * W, cur);
-            if (e + po < a.B) load_state<W>(a.state + (e + po) * W, nxt);
-            draws(e);
-        }
-    }
-#ifdef PBN_STAMPS
-    __builtin_amdgcn_s_waitcnt(0);
-    st[5] = __builtin_amdgcn_s_memrealtime();  // every store of the wave done
-    const uint32_t wv = blockIdx.x * (SB / 64) + threadIdx.x / 64;
-    if ((threadIdx.x & 63) == 0 && wv < 16384) {
-        st[6] = blockIdx.x;
-        st[7] = __smid();
-        for (int k = 0; k < 8; ++k) g_stamps[wv * 8 + k] = st[k];
-    }
-#endif
-}
-
-// The bench shape: every thread owns exactly one env pair (B <= 2 x grid x SB), image staged and both
-// loads issued by k_step. Straight-line, so both envs' threshold rows are read in one LDS round trip
-// and both records in a second (the looped form read env 0's row, its record, env 1's row, its
-// record: three dependent round trips, the uniform tp4 == 4 branch between them), and env 0's plane
-// work waits only for env 0's loads.
-template <int W, int SB>
-__device__ __forceinline__ void k_step_pair(const StepArgs& a, uint8_t* lds, uint64_t e, uint64_t stride,
-                                            const uint64_t (&cur)[W], const uint64_t (&nxt)[W], uint32_t N) {
-    const uint64_t u = a.update_base + (a.ubase_dev ? *a.ubase_dev : 0ull);
-    const uint64_t e1 = e + stride, g0 = a.env_base + e, g1 = g0 + stride;
-    uint32_t n0, c0, n1, c1;
-    if ((a.env_base & 1u) == 0u) {  // envs 2m / 2m + 1 share a Philox call (k_step_single)
-        step_words_paired(a.seed, u, g0, g1, (threadIdx.x & 1u) != 0u, n0, c0, n1, c1);
-    } else {
-        step_words(a.seed, u, g0, n0, c0);
-        step_words(a.seed, u, g1, n1, c1);
-    }
-    const uint32_t i0 = philox_node<KIND_PREDICTOR_MIX>(n0, N), i1 = philox_node<KIND_PREDICTOR_MIX>(n1, N);
-    const Thr32 X = thr32_layout(a.L);
-    uint32_t j0, j1;
-    if (X.tp4 == 4u) {
-        const uint4 t0 = reinterpret_cast<const uint4*>(lds)[i0];
-        const uint4 t1 = reinterpret_cast<const uint4*>(lds)[i1];
-        j0 = (c0 >= t0.x ? 1u : 0u) + (c0 >= t0.y ? 1u : 0u) + (c0 >= t0.z ? 1u : 0u) + (c0 >= t0.w ? 1u : 0u);
-        j1 = (c1 >= t1.x ? 1u : 0u) + (c1 >= t1.y ? 1u : 0u) + (c1 >= t1.z ? 1u : 0u) + (c1 >= t1.w ? 1u : 0u);
-    } else {
-        j0 = predictor_choice32(i0, c0, lds, X.tp4);
-        j1 = predictor_choice32(i1, c1, lds, X.tp4);
-    }
-    const uint64_t* rec = reinterpret_cast<const uint64_t*>(lds + X.rec_off);
-    const uint64_t r0 = rec[__umul24(i0, X.rs) + j0], r1 = rec[__umul24(i1, X.rs) + j1];
-    const PlaneT<SB> P{reinterpret_cast<uint32_t*>(lds + a.L.plane_off) + threadIdx.x};
-    const bool last_dw = N > 64u * W - 32u;  // the plane's last dword holds nodes >= 64W - 32 only
-    auto eval = [&](const uint64_t (&s)[W], uint32_t i, uint64_t r, uint32_t& self) {
-#pragma unroll
-        for (int k = 0; k < W; ++k) {
-            P.put(2 * k, (uint32_t)s[k]);
-            if (k + 1 < W || last_dw) P.put(2 * k + 1, (uint32_t)(s[k] >> 32));
-        }
-        self = P.get(i >> 5);
-        return predictor_apply(P, i, self, r);
-    };
-    auto put = [&](const uint64_t (&s)[W], uint64_t eh, uint32_t i) {  // whole env, bit i flipped
-        uint64_t out[W];
-        const uint32_t wi = i >> 6;
-        const uint64_t m = 1ull << (i & 63u);
-#pragma unroll
-        for (int k = 0; k < W; ++k) out[k] = s[k] ^ ((uint32_t)k == wi ? m : 0ull);
-        store_state<W>(a.state + eh * W, out);
-    };
-    uint32_t self0, self1;
-    const uint32_t y0 = eval(cur, i0, r0, self0);
-    // env 0 is stored before env 1 is evaluated; env 1's loads (issued right behind env 0's) are waited
-    // for first: after a store that may not have been issued, the compiler can only wait vmcnt(0)
-#pragma unroll
-    for (int k = 0; k < W; ++k) asm volatile("" ::"v"(nxt[k]));
-    if (e < a.B && ((self0 >> (i0 & 31u)) & 1u) != y0) put(cur, e, i0);
-    const uint32_t y1 = eval(nxt, i1, r1, self1);  // past B: junk from a clamped load, never stored
-    if (e1 < a.B && ((self1 >> (i1 & 31u)) & 1u) != y1) put(nxt, e1, i1);
-}
-
-// Step mode (T == 1, Philox; REPLAY == 0) and replay mode (REPLAY == 1: T updates from the
-// caller's draws). Rollout (T > 1, Philox) is its own kernel, k_rollout, so that neither
-// path's code shapes the other's register allocation and schedule (sharing one kernel cost
-// the step path 0.6 us per launch at 1M envs).
-template <int W, int KIND, int STORE, int REPLAY, int SB>
-// 1024-thread groups, W <= 4: two workgroups per CU = 8 waves per SIMD, so at most 64 VGPRs (every
-// instance this bound applies to -- both kinds, both store modes, Philox only: SB = 1024 is never
-// launched in replay mode -- compiles without scratch, `make asm`; the stamps build keeps the bound)
-__global__ __launch_bounds__(SB, (SB == 1024 && W <= 4) ? 8 : 1)
-void k_step(StepArgs a) {
-    extern __shared__ __align__(16) uint8_t lds[];
-    const uint64_t stride = (uint64_t)gridDim.x * SB;
-    uint64_t e = (uint64_t)blockIdx.x * SB + threadIdx.x;
-    const uint32_t N = (uint32_t)a.L.n_nodes;
-    uint64_t cur[W];
-    if constexpr (!REPLAY && KIND == KIND_PREDICTOR_MIX && SB == 1024) {
-        // The image's granule (one per thread) is loaded first, then both envs of the pair
-        // (unconditional loads, clamped addresses, so the granule's wait counts only itself:
-        // vmcnt(4)); the granule is written and the barrier passed while the state is in flight,
-        // and the draws follow the barrier. Staged after the draws instead, the barrier waited
-        // for every wave's Philox burst and the state loads: 9.21 -> 8.98 us per launch at 1M envs
-        // (profiles/r02_step_stage_first_ab.txt; phase stamps r02_step_stamps.json)
-        const Thr32 X = thr32_layout(a.L);
-        const uint4* src = reinterpret_cast<const uint4*>(reinterpret_cast<const uint8_t*>(a.img) + a.L.bytes);
-        const uint32_t n16 = X.bytes / 16;
-        uint4 g = make_uint4(0, 0, 0, 0);
-        if (threadIdx.x < n16) g = src[threadIdx.x];
-        uint64_t nx[W];
-        const uint64_t ec = e < a.B ? e : 0, en = e + stride < a.B ? e + stride : 0;
-        load_state<W>(a.state + ec * W, cur);
-        load_state<W>(a.state + en * W, nx);
-        if (threadIdx.x < n16) reinterpret_cast<uint4*>(lds)[threadIdx.x] = g;
-        for (uint32_t k = threadIdx.x + SB; k < n16; k += SB) reinterpret_cast<uint4*>(lds)[k] = src[k];
-        __syncthreads();
-        if (STORE == STORE_DIRTY && 2u * stride >= a.B)
-            k_step_pair<W, SB>(a, lds, e, stride, cur, nx, N);  // one pair per thread (the bench shape)
-        else
-            k_step_single<W, KIND, STORE, SB, true>(a, lds, e, stride, cur, N, &nx);
-        return;
-    }
-    if (e < a.B) load_state<W>(a.state + e * W, cur);
-    if constexpr (!REPLAY) {
-        // Step mode: the draws depend on (seed, update counter, env id) only, so every
-        // draw this thread needs is computed while its state loads are in flight.
-        k_step_single<W, KIND, STORE, SB>(a, lds, e, stride, cur, N);
-    } else {
-        stage_image(reinterpret_cast<const uint4*>(a.img), a.L.bytes / 16, reinterpret_cast<uint4*>(lds));
-        __syncthreads();
-        const PlaneT<SB> P{reinterpret_cast<uint32_t*>(lds + a.L.bytes) + threadIdx.x};
-        while (e < a.B) {
-            const uint64_t en = e + stride;
-            uint64_t nxt[W];
-            if (en < a.B) load_state<W>(a.state + en * W, nxt);  // prefetch the next env
-            to_plane<W>(P, cur);
-            for (uint32_t t = 0; t < a.T; ++t) {
-                const uint32_t i = a.replay_node[(uint64_t)t * a.B + e];
-                uint64_t k53;
-                if (a.replay_k53) {
-                    k53 = a.replay_k53[(uint64_t)t * a.B + e];
-                } else {
-                    // forced node (Graph.step(i=k), base.py:306-308): the node is the caller's, the
-                    // choice word is the env's own Philox step draw of update update_base + t
-                    uint32_t wn, wc;
-                    step_words(a.seed, a.update_base + t, a.env_base + e, wn, wc);
-                    k53 = u32_k53(wc);
-                }
-                if constexpr (KIND == KIND_PREDICTOR_MIX)
-                    predictor_update_lds(P, i, k53, lds, a.L);
-                else
-                    table_update_lds(P, i, k53, lds, a.L);
-            }
-            uint64_t out[W];
-            from_plane<W>(P, out);
-            store_state<W>(a.state + e * W, out);
-#pragma unroll
-            for (int k = 0; k < W; ++k) cur[k] = nxt[k];
-            e = en;
-        }
-    }
-}
-
-// Rollout: T Philox updates per env per launch with the env's state in its LDS plane column;
-// the state is read once and written once (only if it changed).
-template <int W, int KIND, int SB>
-__global__ __launch_bounds__(SB) void k_rollout(StepArgs a) {
-    extern __shared__ __align__(16) uint8_t lds[];
-    const uint64_t stride = (uint64_t)gridDim.x * SB;
-    uint64_t e = (uint64_t)blockIdx.x * SB + threadIdx.x;
-    const uint32_t N = (uint32_t)a.L.n_nodes;
-    uint64_t cur[W];
-    if (e < a.B) load_state<W>(a.state + e * W, cur);
-    const Thr32 X = thr32_layout(a.L);
-    if constexpr (KIND == KIND_PREDICTOR_MIX)  // the compact image (thresholds on the choice word)
-        stage_image(reinterpret_cast<const uint4*>(reinterpret_cast<const uint8_t*>(a.img) + a.L.bytes), X.bytes / 16,
-                    reinterpret_cast<uint4*>(lds));
-    else
-        stage_image(reinterpret_cast<const uint4*>(a.img), a.L.bytes / 16, reinterpret_cast<uint4*>(lds));
-    __syncthreads();
-    const PlaneT<SB> P{reinterpret_cast<uint32_t*>(lds + a.L.plane_off) + threadIdx.x};
-    // Envs 2m / 2m + 1 share their Philox calls (pbn_device.hpp). With an even env base the lane
-    // pair holds such a pair, and for updates t, t + 1 the even lane computes the call of t, the
-    // odd lane that of t + 1, and they swap the two words the other needs: one call per lane
-    // per two updates. Every lane of a wave takes the same trips (lanes past B compute junk
-    // and store nothing), so a partner is never missing.
-    const bool paired = (a.env_base & 1u) == 0u;
-    const bool odd = (threadIdx.x & 1u) != 0u;
-    for (;;) {
-        const bool live = e < a.B;
-        if (__ballot(live) == 0) break;
-        const uint64_t en = e + stride;
-        uint64_t nxt[W];
-        if (en < a.B) load_state<W>(a.state + en * W, nxt);  // prefetch the next env
-        to_plane<W>(P, cur);
-        uint32_t changed = 0;
-        const uint64_t g = a.env_base + e;
-        // node / choice words of updates t and t + 1 of this lane's env
-        auto words2 = [&](uint32_t t, uint32_t& na, uint32_t& ca, uint32_t& nb, uint32_t& cb) {
-            const uint64_t u = a.update_base + t;
-            if (paired) {
-                uint32_t w[4];
-                philox_draw(a.seed, (uint32_t)(u + (odd ? 1u : 0u)), (uint32_t)((u + (odd ? 1u : 0u)) >> 32), g >> 1,
-                            STREAM_STEP, w);
-                const uint32_t r0 = swap_pair_lanes(odd ? w[0] : w[2]), r1 = swap_pair_lanes(odd ? w[1] : w[3]);
-                na = odd ? r0 : w[0];
-                ca = odd ? r1 : w[1];
-                nb = odd ? w[2] : r0;
-                cb = odd ? w[3] : r1;
-            } else {
-                step_words(a.seed, u, g, na, ca);
-                step_words(a.seed, u + 1u, g, nb, cb);
-            }
-        };
-        if constexpr (KIND == KIND_PREDICTOR_MIX) {
-            // software pipeline: the draws and predictor records of updates t + 2, t + 3
-            // (state-independent) are computed while updates t, t + 1 run -- one env per lane
-            // leaves a wave alone on its SIMD at small batches (65,536 envs: one wave per SIMD)
-            uint32_t ia, ib;
-            uint64_t ra, rb;
-            auto draw2 = [&](uint32_t t) {
-                uint32_t na, ca, nb, cb;
-                words2(t, na, ca, nb, cb);
-                ia = philox_node<KIND>(na, N);
-                ib = philox_node<KIND>(nb, N);
-                ra = predictor_record32(ia, ca, lds, X);
-                rb = predictor_record32(ib, cb, lds, X);
-            };
-            auto apply = [&](uint32_t i, uint64_t rec) {
-                const uint32_t d = i >> 5, sh = i & 31u;
-                const uint32_t self = P.get(d);
-                const uint32_t y = predictor_apply(P, i, self, rec);
-                const uint32_t nv = (self & ~(1u << sh)) | (y << sh);
-                P.put(d, nv);
-                changed |= nv != self;
-            };
-            draw2(0);
-            for (uint32_t t = 0; t < a.T; t += 2) {
-                const uint32_t i0 = ia, i1 = ib;
-                const uint64_t r0 = ra, r1 = rb;
-                draw2(t + 2);  // unconditional (past T: junk, unused): no branch before the plane reads
-                apply(i0, r0);
-                if (t + 1 < a.T) apply(i1, r1);
-            }
-        } else {
-            for (uint32_t t = 0; t < a.T; t += 2) {
-                uint32_t na, ca, nb, cb;
-                words2(t, na, ca, nb, cb);
-                changed |= table_update_lds(P, philox_node<KIND>(na, N), u32_k53(ca), lds, a.L);
-                if (t + 1 < a.T) changed |= table_update_lds(P, philox_node<KIND>(nb, N), u32_k53(cb), lds, a.L);
-            }
-        }
-        uint64_t out[W];
-        from_plane<W>(P, out);
-        bool diff = false;  // whole env, only if it differs (see k_step_single)
-#pragma unroll
-        for (int k = 0; k < W; ++k) diff |= out[k] != cur[k];
-        if (live && changed && diff) store_state<W>(a.state + e * W, out);
-#pragma unroll
-        for (int k = 0; k < W; ++k) cur[k] = nxt[k];
-        e = en;
-    }
-}
-
-// ------------------------------------------------------------------ init / reset
-template <int W>
-__global__ __launch_bounds__(BLOCK) void k_init(InitArgs a) {
-    const uint64_t e = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (e >= a.B) return;
-    if (a.mask && !a.mask[e]) return;
-    const uint64_t g = a.env_base + e;
-    uint64_t s[W];
-#pragma unroll
-    for (int m = 0; 2 * m < W; ++m) {
-        uint32_t w[4];
-        philox_draw(a.seed, (uint32_t)m + (a.cube_care ? 1u : 0u), a.reset_count, g,
-                    a.cube_care ? STREAM_RESET : STREAM_INIT, w);
-        s[2 * m] = ((uint64_t)w[1] << 32) | w[0];
-        if (2 * m + 1 < W) s[2 * m + 1] = ((uint64_t)w[3] << 32) | w[2];
-    }
-    if (a.cube_care) {
-        uint32_t w[4];
-        philox_draw(a.seed, 0u, a.reset_count, g, STREAM_RESET, w);
-        const uint32_t c = __umulhi(w[0], (uint32_t)a.n_cubes);
-#pragma unroll
-        for (int k = 0; k < W; ++k) {
-            const uint64_t care = a.cube_care[(uint64_t)c * W + k];
-            s[k] = (a.cube_value[(uint64_t)c * W + k] & care) | (s[k] & ~care);
-        }
-    }
-    const int r = a.n_nodes & 63;
-    if (r) s[W - 1] &= (((uint64_t)1 << r) - 1);
-    if (a.kind == KIND_PROB_TABLE) s[0] &= ~(uint64_t)1;  // pbn.py:118 state[0] = 0
-    store_state<W>(a.state + e * W, s);
-    if (a.n_steps) a.n_steps[e] = 0;
-}
-
-// Python list indexing of flipNode(a - offset): valid for -N <= idx < N.
-__device__ __forceinline__ bool action_node(int32_t a, int32_t offset, int32_t N, uint32_t* node) {
-    const int32_t idx = a - offset;
-    if (idx >= N || idx < -N) return false;
-    *node = (uint32_t)(idx < 0 ? idx + N : idx);
-    return true;
-}
-
-// Flip every (unique, if dedup) non-zero action of the row; returns the number of
-// actions counted by the reference's reward (unique values incl. 0, or A).
-template <int W>
-__device__ __forceinline__ int apply_actions(uint64_t (&s)[W], const int32_t* row, int32_t A, int32_t offset,
-                                             int32_t dedup, int32_t N, bool* bad) {
-    int n_act = 0;
-    for (int32_t k = 0; k < A; ++k) {
-        const int32_t v = row[k];
-        bool dup = false;
-        if (dedup)
-            for (int32_t q = 0; q < k; ++q) dup |= (row[q] == v);
-        if (dup) continue;
-        ++n_act;
-        if (v == 0) continue;
-        uint32_t node;
-        if (!action_node(v, offset, N, &node)) {
-            *bad = true;
-            continue;
-        }
-        setbit<W>(s, node, getbit<W>(s, node) ^ 1u);
-    }
-    return dedup ? n_act : A;
-}
-
-template <int W>
-__global__ __launch_bounds__(BLOCK) void k_flip(FlipArgs a) {
-    const uint64_t e = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (e >= a.B) return;
-    uint64_t s[W];
-    load_state<W>(a.state + e * W, s);
-    bool bad = false;
-    apply_actions<W>(s, a.actions + e * (uint64_t)a.A, a.A, a.offset, a.dedup, a.n_nodes, &bad);
-    if (bad) {
-        atomicOr(a.error, 1);
-        return;  // leave this env untouched
-    }
-    store_state<W>(a.state + e * W, s);
-}
-
 // ------------------------------------------------------------------ R6 env step
-template <int W>
-__device__ __forceinline__ bool cube_match(const uint64_t (&s)[W], const uint64_t* cv) {
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < W; ++k) ok &= ((s[k] & cv[k]) == cv[W + k]);
-    return ok;
-}
-
-template <int W>
-__device__ __forceinline__ bool attracting(const uint64_t (&s)[W], const uint64_t* cubes, int32_t H) {
-    bool hit = false;
-    for (int32_t h = 0; h < H && !hit; ++h) hit = cube_match<W>(s, cubes + (uint64_t)h * 2 * W);
-    return hit;
-}
-
-// Mismatch count of a state against one cube: #cared bits that differ from the cube.
-template <int W>
-__device__ __forceinline__ uint32_t cube_mismatch(const uint64_t (&s)[W], const uint64_t* cv) {
-    uint32_t m = 0;
-#pragma unroll
-    for (int k = 0; k < W; ++k) m += (uint32_t)__popcll((s[k] & cv[k]) ^ cv[W + k]);
-    return m;
-}
-
-template <int W, class P_t>
-__device__ __forceinline__ bool attracting_plane(const P_t& P, const uint64_t* cubes, int32_t H) {
-    uint64_t s[W];
-    from_plane<W>(P, s);
-    return attracting<W>(s, cubes, H);
-}
-
 // PBNTargetMultiEnv.step (pbn_target_multi.py:119-154) for every env of the batch.
 //
 // Persistent waves with lane refill: a lane that finishes its env takes the next
@@ -585,8 +48,6 @@ __device__ __forceinline__ bool attracting_plane(const P_t& P, const uint64_t* c
 // active this is the same Philox work per lane; in the tail, when a few lanes run long
 // (capped) loops, idle lanes generate their draws and the per-update cost drops to the
 // state read/write.
-
-__device__ __forceinline__ uint32_t has_zero_byte(uint32_t v) { return (v - 0x01010101u) & ~v & 0x80808080u; }
 
 #ifndef PBN_ENV_OWN_DRAWS_MIN
 #define PBN_ENV_OWN_DRAWS_MIN 40  // measurement builds (tools/build_exp.sh) change this
@@ -618,31 +79,6 @@ struct RankMagic {
     }
 };
 __constant__ constexpr RankMagic kRankMagic{};
-
-// Inclusive prefix sum over the wave's 64 lanes (row_shr 1/2/4/8 inside each 16-lane row, then
-// row_bcast15 / row_bcast31 carry the row totals; lanes without a source add 0).
-// Inclusive max over the wave (the same DPP pattern; lanes without a source take 0): lane 63 holds the max.
-__device__ __forceinline__ uint32_t wave_inclusive_max(uint32_t x) {
-    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xF, 0xF, false));
-    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xF, 0xF, false));
-    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xF, 0xF, false));
-    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xF, 0xF, false));
-    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xA, 0xF, false));
-    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xC, 0xF, false));
-    return x;
-}
-
-__device__ __forceinline__ uint32_t wave_inclusive_add(uint32_t x) {
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xF, 0xF, false);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xF, 0xF, false);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xF, 0xF, false);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xF, 0xF, false);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xA, 0xF, false);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xC, 0xF, false);
-    return x;
-}
-
-
 
 // A wave's draw buffer (env_gen_wave_bytes(chunk)) in tail mode: the per-node 64-bit writer masks from
 // byte 0 (N <= 512 nodes: 4 KiB), the hand-off flag at chunk * 128 and the hand-off box (5 + 2W words)
@@ -756,11 +192,6 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
     int n_act = 0;
     bool capped = false;
     bool tmode = false;  // TAIL: this wave resolves its remaining envs one at a time, 64 updates per block
-    auto wave_sync = [] {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
 
     // ---- hand-off of tail envs between the waves of a workgroup (TAIL, EnvArgs::steal_local), in LDS.
     // A wave in tail mode resolves its live envs one after another, so a long until-attractor loop
@@ -2252,657 +1683,24 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
 #endif
 }
 
-// ------------------------------------------------------------------ R6, group mode
-// The same env step with G lanes per env: a block of G consecutive updates of one env is
-// evaluated by the G lanes at once (parallel in time), so one env advances G updates per
-// round trip instead of one. The draws of the block do not depend on the state (Philox
-// counter = update index), so lane k knows its node i_k and predictor record up front;
-// what it needs are the values of its 4 input nodes at time k, i.e. the output of the
-// last update j < k in the block that wrote each input, or the block-start value. The
-// writers are found from the byte-packed node list of the group; the outputs y_k are
-// then the fixed point of y_k = tt_k(inputs from writers), a DAG of depth < G: every
-// round that changes nothing is exact. Per-update mismatch deltas are prefix-summed
-// across the group (packed byte counters, as in k_env), the first update whose counters
-// hit a cube ends the env step, and the final writer of each node in the committed
-// prefix sets its bit in the env's LDS row (ds_or / ds_and: distinct nodes, possibly one
-// dword). Same Philox counters as k_env, so the results are bit-identical to lane mode.
-//
-// Used where the batch is small against the chip (BASELINE config 5: 131,072 envs per
-// GPU): there lane mode is latency-bound on the tail of long until-attractor loops.
-// Requirements: predictor mix, N <= 256 (byte-packed node list), fast byte counters.
-
-template <int G>
-__device__ __forceinline__ uint32_t grp_bcast(uint32_t v, uint32_t j) {
-    static_assert(G == 2 || G == 4 || G == 8, "group size");
-    if constexpr (G <= 4) {
-        // quad_perm [j,j,j,j] (G == 2: lanes 0/1 and 2/3 of each quad form two groups)
-        switch (j) {
-            case 0: return G == 2 ? (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xA0, 0xF, 0xF, false)   // [0,0,2,2]
-                                  : (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x00, 0xF, 0xF, false);  // [0,0,0,0]
-            case 1: return G == 2 ? (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xF5, 0xF, 0xF, false)   // [1,1,3,3]
-                                  : (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x55, 0xF, 0xF, false);  // [1,1,1,1]
-            case 2: return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xAA, 0xF, 0xF, false);
-            default: return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xFF, 0xF, 0xF, false);
-        }
-    } else {
-        // ds_swizzle bit-mask mode within 32 lanes: src = (lane & 0x18) | j
-        switch (j) {
-            case 0: return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x18 | (0 << 5));
-            case 1: return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x18 | (1 << 5));
-            case 2: return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x18 | (2 << 5));
-            case 3: return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x18 | (3 << 5));
-            case 4: return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x18 | (4 << 5));
-            case 5: return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x18 | (5 << 5));
-            case 6: return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x18 | (6 << 5));
-            default: return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x18 | (7 << 5));
-        }
-    }
-}
-
-// value of lane (lane - n) of the same 16-lane row, 0 where that lane is outside the row
-template <int N_>
-__device__ __forceinline__ uint32_t row_shr(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x110 + N_, 0xF, 0xF, true);
-}
-
-// 0x80 in every byte of v that is zero (exact, no false positives)
-__device__ __forceinline__ uint32_t zero_bytes(uint32_t v) {
-    return ~(((v & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | v | 0x7F7F7F7Fu);
-}
-
-// Byte-packed node list of a group (G <= 8: two words). match(x) -> 0x80 per byte j with i_j == x.
-template <int G>
-struct GroupNodes {
-    uint32_t lo = 0, hi = 0;
-    __device__ __forceinline__ explicit GroupNodes(uint32_t i) {
-#pragma unroll
-        for (int j = 0; j < G; ++j) {
-            const uint32_t v = grp_bcast<G>(i, (uint32_t)j);
-            if (j < 4)
-                lo |= v << (8 * j);
-            else
-                hi |= v << (8 * (j - 4));
-        }
-        if (G < 4) lo |= 0xFFFFFFFFu << (8 * G);  // unused bytes never match (node < 256)
-        if (G <= 4) hi = 0xFFFFFFFFu;
-    }
-    // bytes j in [j0, j1) of the list equal to x, as a bit mask over j
-    __device__ __forceinline__ uint32_t match(uint32_t x, uint32_t j0, uint32_t j1) const {
-        const uint32_t xx = x * 0x01010101u;
-        const uint32_t zl = zero_bytes(lo ^ xx), zh = zero_bytes(hi ^ xx);
-        // compress 0x80 per byte to one bit per byte
-        uint32_t m = ((zl >> 7) & 1u) | ((zl >> 14) & 2u) | ((zl >> 21) & 4u) | ((zl >> 28) & 8u);
-        if (G > 4) m |= (((zh >> 7) & 1u) | ((zh >> 14) & 2u) | ((zh >> 21) & 4u) | ((zh >> 28) & 8u)) << 4;
-        const uint32_t rng = ((1u << j1) - 1u) & ~((1u << j0) - 1u);
-        return m & rng;
-    }
-};
-
-// One block of G consecutive updates of a group's env, lane k holding update k: node i, its
-// predictor record and the block-start values v of its operands (in0, in1, in2, self). Returns
-// y (node i's new value) and old (its value right before update k), exact in every lane.
-template <int G>
-struct GrpBlock {
-    uint32_t y = 0, old = 0;
-    uint32_t ip = 0;  // G == 2: the partner lane's node
-    GroupNodes<G> nodes;
-    __device__ __forceinline__ explicit GrpBlock(uint32_t i) : nodes(G == 2 ? 0u : i) {}
-    // update k is the last writer of node i among the first n_done updates of the block
-    __device__ __forceinline__ bool last(uint32_t i, uint32_t k, uint32_t n_done) const {
-        return G == 2 ? (k == 1 || n_done < 2 || ip != i) : nodes.match(i, k + 1, n_done) == 0u;
-    }
-};
-
-template <int G>
-__device__ __forceinline__ GrpBlock<G> grp_resolve(uint32_t i, uint64_t rec, const uint32_t (&in)[4],
-                                                   const uint32_t (&v)[4], uint32_t k, uint32_t gbase,
-                                                   uint32_t gmask) {
-    GrpBlock<G> b(i);
-    const uint32_t tt = (uint32_t)(rec >> 48);
-    auto tt_of = [&](const uint32_t (&x)[4]) { return (tt >> ((x[0] << 3) | (x[1] << 2) | (x[2] << 1) | x[3])) & 1u; };
-    if constexpr (G == 2) {
-        // pairs: lane 1 depends on lane 0 only where an input is lane 0's node
-        b.ip = (uint32_t)__builtin_amdgcn_mov_dpp((int)i, 0xB1, 0xF, 0xF, false);  // quad_perm [1,0,3,2]
-        const uint32_t y0 = tt_of(v);  // exact in lane 0
-        const uint32_t yb = (uint32_t)__builtin_amdgcn_mov_dpp((int)y0, 0xA0, 0xF, 0xF, false);  // [0,0,2,2]
-        uint32_t x[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) x[q] = (k == 1 && in[q] == b.ip) ? yb : v[q];
-        b.y = tt_of(x);
-        b.old = x[3];
-    } else {
-        int32_t wr[4];  // last writer j < k of each input, or -1
-        bool dep = false;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const uint32_t mm = b.nodes.match(in[q], 0, k);
-            wr[q] = mm ? 31 - __clz((int)mm) : -1;
-            dep |= mm != 0;
-        }
-        auto eval = [&](uint32_t Y, uint32_t* self_old) {
-            uint32_t x[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) x[q] = wr[q] >= 0 ? (Y >> wr[q]) & 1u : v[q];
-            *self_old = x[3];
-            return tt_of(x);
-        };
-        b.y = eval(0u, &b.old);  // exact where no input has an in-block writer
-        if (__ballot(dep) != 0) {
-            // after round r lanes 0..r are exact, so round G - 1 at the latest changes nothing;
-            // a round that changes nothing has `old` computed from the final outputs
-#pragma unroll 1
-            for (int r = 0; r < G; ++r) {
-                const uint32_t Y = (uint32_t)(__ballot(b.y != 0u) >> gbase) & gmask;
-                const uint32_t yn = eval(Y, &b.old);
-                if (__ballot(yn != b.y) == 0) break;
-                b.y = yn;
-            }
-        }
-    }
-    return b;
-}
-
-template <int W, int G>
-__global__ __launch_bounds__(BLOCK) void k_env_grp(EnvArgs a) {
-    extern __shared__ __align__(16) uint8_t lds[];
-    stage_image(reinterpret_cast<const uint4*>(a.img), a.L.bytes / 16, reinterpret_cast<uint4*>(lds));
-    __syncthreads();
-    const uint32_t N = (uint32_t)a.L.n_nodes;
-    const uint64_t* cubes = reinterpret_cast<const uint64_t*>(lds + a.off_cubes);
-    const uint64_t* target = reinterpret_cast<const uint64_t*>(lds + a.off_target);
-    const uint2* ndelta = reinterpret_cast<const uint2*>(lds + a.off_ndelta);
-    const uint64_t* recs = reinterpret_cast<const uint64_t*>(lds + a.L.off_rec);
-    const int32_t H = a.n_cubes;
-    const uint32_t lane = __lane_id();
-    const uint32_t k = lane & (G - 1);                     // position in the group = update slot
-    const uint32_t gbase = lane & ~(uint32_t)(G - 1);
-    const uint32_t gmask = (1u << G) - 1u;
-    // the env's 2W dwords, one row per group (bank = group * 2W + dword: 8 groups of W = 4 fill 64 banks)
-    uint32_t* row = reinterpret_cast<uint32_t*>(lds + a.off_gen) + (threadIdx.x / G) * (2 * W);
-    auto wave_sync = [] {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
-
-    // per-env registers, identical in every lane of the group
-    int64_t e = -1;
-    uint32_t t = 0;  // env step of this launch
-    bool exhausted = false;
-    uint64_t o0[W];
-    uint32_t m_lo = 0, m_hi = 0, used = 0;
-    bool hit0 = false;
-    int64_t nst = 0;
-    int n_act = 0;
-    uint64_t gid = 0;
-
-    // step t (or the first later step with a valid action row) of env e from state s; with no
-    // step left, write the env back and free the group (as begin_steps in k_env)
-    auto begin_steps = [&](uint64_t (&s)[W]) {
-        for (; t < a.n_calls; ++t) {
-            uint64_t f[W];
-#pragma unroll
-            for (int q = 0; q < W; ++q) f[q] = s[q];
-            bool bad = false;
-            n_act = apply_actions<W>(f, a.actions + ((uint64_t)t * a.B + (uint64_t)e) * (uint64_t)a.A, a.A,
-                                     a.offset, a.dedup, (int32_t)N, &bad);
-            if (bad) {  // reference raises ValueError; this env step is skipped, the env left untouched
-                if (k == 0) atomicOr(a.error, 1);
-                continue;
-            }
-            ++nst;  // :123
-#pragma unroll
-            for (int q = 0; q < W; ++q) o0[q] = f[q];  // :133 observation before the update
-            if (k == 0) {
-#pragma unroll
-                for (int q = 0; q < W; ++q) {
-                    row[2 * q] = (uint32_t)f[q];
-                    row[2 * q + 1] = (uint32_t)(f[q] >> 32);
-                }
-            }
-            uint32_t m[2] = {0x01010101u, 0x01010101u};  // unused cubes: never zero
-            for (int32_t h = 0; h < H; ++h) {
-                const uint32_t c = cube_mismatch<W>(f, cubes + (uint64_t)h * 2 * W);
-                const uint32_t sh = 8u * (uint32_t)(h & 3);
-                m[h >> 2] = (m[h >> 2] & ~(0xFFu << sh)) | (c << sh);
-            }
-            m_lo = m[0];
-            m_hi = m[1];
-            hit0 = (has_zero_byte(m_lo) | has_zero_byte(m_hi)) != 0u;
-            used = 0;
-            return;
-        }
-        if (k == 0) {
-            store_state<W>(a.state + (uint64_t)e * W, s);
-            a.n_steps[e] = nst;
-        }
-        e = -1;
-    };
-
-    for (;;) {
-        // ---- refill groups without an env: one atomic per wave, ranks over the groups' leaders
-        const bool need = e < 0 && !exhausted;
-        const uint64_t need_lead = __ballot(need && k == 0);
-        if (need_lead) {
-            const uint32_t leader = (uint32_t)__ffsll((unsigned long long)need_lead) - 1u;
-            unsigned long long base = 0;
-            if (lane == leader) base = atomicAdd(a.counter, (unsigned long long)__popcll(need_lead));
-            base = __shfl(base, (int)leader);
-            if (need) {
-                const uint64_t ne = base + (uint64_t)__popcll(need_lead & ((1ull << gbase) - 1ull));
-                if (ne >= a.B) {
-                    exhausted = true;
-                } else {
-                    uint64_t s[W];
-                    load_state<W>(a.state + ne * W, s);  // every lane of the group: one request
-                    e = (int64_t)ne;
-                    gid = a.env_base + ne;
-                    t = 0;
-                    nst = a.n_steps[ne];
-                    begin_steps(s);
-                }
-            }
-            wave_sync();
-        }
-        if (__ballot(e >= 0) == 0) {
-            if (__ballot(!exhausted) == 0) break;
-            continue;
-        }
-
-        // ---- one block: update used + k of this group's env in lane k (idle groups compute junk)
-        // (a block starts at a multiple of G: lanes 2m and 2m + 1 share Philox call (used >> 1) + m)
-        uint32_t w4[4];
-        philox_draw(a.seed, (used + k) >> 1, a.call_idx + t, gid, STREAM_ENV, w4);
-        const uint32_t i = philox_node<KIND_PREDICTOR_MIX>((k & 1u) ? w4[2] : w4[0], N);
-        const uint64_t rec = recs[i * a.L.pmax + predictor_choice(i, u32_k53((k & 1u) ? w4[3] : w4[1]), lds, a.L)];
-        const uint2 nd = ndelta[i];
-        const uint32_t in[4] = {(uint32_t)rec & 0xFFFFu, (uint32_t)(rec >> 16) & 0xFFFFu,
-                                (uint32_t)(rec >> 32) & 0xFFFFu, i};
-        uint32_t v[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = (row[in[q] >> 5] >> (in[q] & 31u)) & 1u;  // block-start values
-        const GrpBlock<G> blk = grp_resolve<G>(i, rec, in, v, k, gbase, gmask);
-        const uint32_t y = blk.y, old = blk.old;
-        // mismatch counters after each update of the block (inclusive prefix over the group)
-        const bool changed = y != old;
-        uint32_t dl = changed ? (y ? nd.x : 0u - nd.x) : 0u;
-        uint32_t dh = changed ? (y ? nd.y : 0u - nd.y) : 0u;
-        {
-            uint32_t tl = row_shr<1>(dl), th = row_shr<1>(dh);
-            dl += k >= 1 ? tl : 0u;
-            dh += k >= 1 ? th : 0u;
-            if constexpr (G >= 4) {
-                tl = row_shr<2>(dl);
-                th = row_shr<2>(dh);
-                dl += k >= 2 ? tl : 0u;
-                dh += k >= 2 ? th : 0u;
-            }
-            if constexpr (G >= 8) {
-                tl = row_shr<4>(dl);
-                th = row_shr<4>(dh);
-                dl += k >= 4 ? tl : 0u;
-                dh += k >= 4 ? th : 0u;
-            }
-        }
-        const uint32_t ml = m_lo + dl, mh = m_hi + dh;
-        const bool valid = used + k < a.update_cap;
-        const bool hit = (used + k == 0 && !a.first_tested) ? hit0 : (has_zero_byte(ml) | has_zero_byte(mh)) != 0u;
-        const uint32_t SM = (uint32_t)(__ballot(valid && hit) >> gbase) & gmask;
-        const uint32_t VM = (uint32_t)(__ballot(valid) >> gbase) & gmask;
-        const uint32_t n_done = SM ? (uint32_t)__ffs((int)SM) : (uint32_t)__popc(VM);
-        const bool done = SM != 0u || used + n_done >= a.update_cap;
-        const bool capped = SM == 0u;  // only meaningful when done
-        // commit: the last writer of each node among the first n_done updates sets its bit
-        const bool last = blk.last(i, k, n_done);
-        if (e >= 0 && k < n_done && y != v[3] && last) {
-            if (y)
-                atomicOr(&row[i >> 5], 1u << (i & 31u));
-            else
-                atomicAnd(&row[i >> 5], ~(1u << (i & 31u)));
-        }
-        uint32_t nl, nh;  // counters after the last committed update
-        if constexpr (G == 2) {
-            const uint32_t l1 = (uint32_t)__builtin_amdgcn_mov_dpp((int)ml, 0xF5, 0xF, 0xF, false);  // [1,1,3,3]
-            const uint32_t h1 = (uint32_t)__builtin_amdgcn_mov_dpp((int)mh, 0xF5, 0xF, 0xF, false);
-            const uint32_t l0 = (uint32_t)__builtin_amdgcn_mov_dpp((int)ml, 0xA0, 0xF, 0xF, false);  // [0,0,2,2]
-            const uint32_t h0 = (uint32_t)__builtin_amdgcn_mov_dpp((int)mh, 0xA0, 0xF, 0xF, false);
-            nl = n_done == 2 ? l1 : l0;
-            nh = n_done == 2 ? h1 : h0;
-        } else {
-            const uint32_t src = gbase + (n_done ? n_done - 1u : 0u);
-            nl = (uint32_t)__shfl((int)ml, (int)src);
-            nh = (uint32_t)__shfl((int)mh, (int)src);
-        }
-        if (e >= 0 && n_done) {
-            m_lo = nl;
-            m_hi = nh;
-        }
-        wave_sync();
-        if (e < 0) continue;
-        used += n_done;
-        if (!done) continue;
-
-        // ---- finish: outputs of step() (:148-154) into step t's slot (group leader), next step
-        uint64_t s[W];
-#pragma unroll
-        for (int q = 0; q < W; ++q) s[q] = (uint64_t)row[2 * q] | ((uint64_t)row[2 * q + 1] << 32);
-        if (k == 0) {
-            uint64_t o[W];
-#pragma unroll
-            for (int q = 0; q < W; ++q) o[q] = (used <= 1 && !a.first_tested) ? o0[q] : s[q];
-            const uint64_t eo = (uint64_t)t * a.B + (uint64_t)e;
-            store_state<W>(a.obs + eo * W, o);
-            const bool term = cube_match<W>(o, target);  // :190-199 (target[0] only)
-            a.reward[eo] = (term ? a.reward_success : 0) - a.action_cost * n_act;  // :218-222
-            a.flags[eo] = (uint8_t)((term ? 1 : 0) | (nst == a.horizon ? 2 : 0) | (capped ? 4 : 0));
-            a.n_updates[eo] = used;
-        }
-        wave_sync();  // every lane's row reads before the next step rewrites the row
-        ++t;
-        begin_steps(s);
-        wave_sync();
-    }
-}
-
-// ------------------------------------------------------------------ rollout, group mode
-// k_rollout with G lanes per env (predictor mix, N <= 256): each block of G consecutive updates
-// is resolved at once by grp_resolve (the same machinery as k_env_grp), the env's state kept as
-// one LDS row per group. Same Philox counters as k_rollout, so the same states. For batches too
-// small to give every SIMD several waves in lane mode (BASELINE config 2: 65,536 envs = one
-// wave per SIMD), where one env per lane is latency-bound on its own update chain.
-template <int W, int G>
-__global__ __launch_bounds__(BLOCK) void k_rollout_grp(StepArgs a) {
-    extern __shared__ __align__(16) uint8_t lds[];
-    const Thr32 X = thr32_layout(a.L);  // the compact image (thresholds on the choice word)
-    stage_image(reinterpret_cast<const uint4*>(reinterpret_cast<const uint8_t*>(a.img) + a.L.bytes), X.bytes / 16,
-                reinterpret_cast<uint4*>(lds));
-    __syncthreads();
-    const uint32_t N = (uint32_t)a.L.n_nodes;
-    const uint32_t lane = __lane_id();
-    const uint32_t k = lane & (G - 1);
-    const uint32_t gbase = lane & ~(uint32_t)(G - 1);
-    const uint32_t gmask = (1u << G) - 1u;
-    uint32_t* row = reinterpret_cast<uint32_t*>(lds + a.L.plane_off) + (threadIdx.x / G) * (2 * W);
-    auto wave_sync = [] {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
-    const uint64_t groups = (uint64_t)gridDim.x * (BLOCK / G);
-    // every group of a wave takes the same number of trips (ballots and wave syncs inside)
-    for (uint64_t e = (uint64_t)blockIdx.x * (BLOCK / G) + threadIdx.x / G;; e += groups) {
-        const bool live = e < a.B;
-        if (__ballot(live) == 0) break;
-        uint64_t s[W];
-        if (live) {
-            load_state<W>(a.state + e * W, s);
-            if (k == 0) {
-#pragma unroll
-                for (int q = 0; q < W; ++q) {
-                    row[2 * q] = (uint32_t)s[q];
-                    row[2 * q + 1] = (uint32_t)(s[q] >> 32);
-                }
-            }
-        }
-        wave_sync();
-        const uint64_t g = a.env_base + e;
-        for (uint32_t used = 0; used < a.T; used += G) {
-            uint32_t nw, cw;
-            step_words(a.seed, a.update_base + used + k, g, nw, cw);
-            const uint32_t i = philox_node<KIND_PREDICTOR_MIX>(nw, N);
-            const uint64_t rec = predictor_record32(i, cw, lds, X);
-            const uint32_t in[4] = {(uint32_t)rec & 0xFFFFu, (uint32_t)(rec >> 16) & 0xFFFFu,
-                                    (uint32_t)(rec >> 32) & 0xFFFFu, i};
-            uint32_t v[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) v[q] = (row[in[q] >> 5] >> (in[q] & 31u)) & 1u;  // block-start values
-            const GrpBlock<G> blk = grp_resolve<G>(i, rec, in, v, k, gbase, gmask);
-            const uint32_t n_done = min((uint32_t)G, a.T - used);
-            // the last writer of each node among the block's valid updates sets its bit
-            if (live && k < n_done && blk.y != v[3] && blk.last(i, k, n_done)) {
-                if (blk.y)
-                    atomicOr(&row[i >> 5], 1u << (i & 31u));
-                else
-                    atomicAnd(&row[i >> 5], ~(1u << (i & 31u)));
-            }
-            wave_sync();
-        }
-        if (live && k == 0) {
-            uint64_t out[W];
-            bool diff = false;  // whole env, only if it differs (see k_step_single)
-#pragma unroll
-            for (int q = 0; q < W; ++q) {
-                out[q] = (uint64_t)row[2 * q] | ((uint64_t)row[2 * q + 1] << 32);
-                diff |= out[q] != s[q];
-            }
-            if (diff) store_state<W>(a.state + e * W, out);
-        }
-        wave_sync();  // the row is rewritten by the group's next env
-    }
-}
-
 // ------------------------------------------------------------------ dispatch
-template <int W, int KIND>
-static void* step_fn(int store, int replay, int sb, int rollout, int grp) {
-    if (replay) return (void*)k_step<W, KIND, STORE_FULL, 1, BLOCK>;
-    if constexpr (KIND == KIND_PREDICTOR_MIX && W <= 4) {
-        if (rollout && grp == 2) return (void*)k_rollout_grp<W, 2>;
-        if (rollout && grp == 4) return (void*)k_rollout_grp<W, 4>;
-        if (rollout && grp == 8) return (void*)k_rollout_grp<W, 8>;
-    }
-    if (grp > 1) return nullptr;
-    if (rollout) return sb == 1024 ? (void*)k_rollout<W, KIND, 1024> : (void*)k_rollout<W, KIND, BLOCK>;
-    if (sb == 1024)
-        return store == STORE_DIRTY ? (void*)k_step<W, KIND, STORE_DIRTY, 0, 1024>
-                                    : (void*)k_step<W, KIND, STORE_FULL, 0, 1024>;
-    return store == STORE_DIRTY ? (void*)k_step<W, KIND, STORE_DIRTY, 0, BLOCK>
-                                : (void*)k_step<W, KIND, STORE_FULL, 0, BLOCK>;
-}
-
-template <int KIND>
-static void* step_fn_w(int W, int store, int replay, int sb, int rollout, int grp) {
-    switch (W) {
-        case 1: return step_fn<1, KIND>(store, replay, sb, rollout, grp);
-        case 2: return step_fn<2, KIND>(store, replay, sb, rollout, grp);
-        case 3: return step_fn<3, KIND>(store, replay, sb, rollout, grp);
-        case 4: return step_fn<4, KIND>(store, replay, sb, rollout, grp);
-        case 5: return step_fn<5, KIND>(store, replay, sb, rollout, grp);
-        case 6: return step_fn<6, KIND>(store, replay, sb, rollout, grp);
-        case 7: return step_fn<7, KIND>(store, replay, sb, rollout, grp);
-        case 8: return step_fn<8, KIND>(store, replay, sb, rollout, grp);
-    }
-    return nullptr;
-}
-
-template <int G>
-static void* env_grp_fn(int W) {
-    switch (W) {
-        case 1: return (void*)k_env_grp<1, G>;
-        case 2: return (void*)k_env_grp<2, G>;
-        case 3: return (void*)k_env_grp<3, G>;
-        case 4: return (void*)k_env_grp<4, G>;
-    }
-    return nullptr;  // N <= 256
-}
-
 template <int KIND>
 static void* env_fn_w(int W, int replay, int fast, int grp) {
     if (fast == 3) {
         if (KIND != KIND_PREDICTOR_MIX || replay) return nullptr;
-        return grp == 2 ? env_grp_fn<2>(W) : grp == 4 ? env_grp_fn<4>(W) : grp == 8 ? env_grp_fn<8>(W) : nullptr;
+        return env_grp_kernel(W, grp);
     }
-#define PBN_ENV_CASE(w)                                                                  \
-    case w:                                                                              \
-        if (fast == 2 && KIND == KIND_PREDICTOR_MIX && !replay) return (void*)k_env<w, KIND_PREDICTOR_MIX, 0, 2>; \
-        if (fast == 4 && KIND == KIND_PREDICTOR_MIX && !replay) return (void*)k_env<w, KIND_PREDICTOR_MIX, 0, 4>; \
-        if (fast) return replay ? (void*)k_env<w, KIND, 1, 1> : (void*)k_env<w, KIND, 0, 1>; \
+    return by_words<8>(W, [=](auto w) {
+        if (fast == 2 && KIND == KIND_PREDICTOR_MIX && !replay) return (void*)k_env<w, KIND_PREDICTOR_MIX, 0, 2>;
+        if (fast == 4 && KIND == KIND_PREDICTOR_MIX && !replay) return (void*)k_env<w, KIND_PREDICTOR_MIX, 0, 4>;
+        if (fast) return replay ? (void*)k_env<w, KIND, 1, 1> : (void*)k_env<w, KIND, 0, 1>;
         return replay ? (void*)k_env<w, KIND, 1, 0> : (void*)k_env<w, KIND, 0, 0>;
-    switch (W) {
-        PBN_ENV_CASE(1)
-        PBN_ENV_CASE(2)
-        PBN_ENV_CASE(3)
-        PBN_ENV_CASE(4)
-        PBN_ENV_CASE(5)
-        PBN_ENV_CASE(6)
-        PBN_ENV_CASE(7)
-        PBN_ENV_CASE(8)
-    }
-#undef PBN_ENV_CASE
-    return nullptr;
+    });
 }
 
-static void* init_fn(int W) {
-    switch (W) {
-        case 1: return (void*)k_init<1>;
-        case 2: return (void*)k_init<2>;
-        case 3: return (void*)k_init<3>;
-        case 4: return (void*)k_init<4>;
-        case 5: return (void*)k_init<5>;
-        case 6: return (void*)k_init<6>;
-        case 7: return (void*)k_init<7>;
-        case 8: return (void*)k_init<8>;
-    }
-    return nullptr;
-}
-
-static void* flip_fn(int W) {
-    switch (W) {
-        case 1: return (void*)k_flip<1>;
-        case 2: return (void*)k_flip<2>;
-        case 3: return (void*)k_flip<3>;
-        case 4: return (void*)k_flip<4>;
-        case 5: return (void*)k_flip<5>;
-        case 6: return (void*)k_flip<6>;
-        case 7: return (void*)k_flip<7>;
-        case 8: return (void*)k_flip<8>;
-    }
-    return nullptr;
-}
-
-static int launch(void* fn, int grid, uint32_t lds, void* stream, void* args, size_t args_size, int block = BLOCK) {
-    if (!fn) return (int)hipErrorInvalidValue;
-    (void)args_size;
-    void* kargs[] = {args};
-    return (int)hipLaunchKernel(fn, dim3((unsigned)grid), dim3((unsigned)block), kargs, lds, (hipStream_t)stream);
-}
-
-uint32_t step_lds_bytes(int W, uint32_t image_bytes, int sb, int grp) {
-    if (grp > 1) return image_bytes + 8u * (uint32_t)W * (BLOCK / (uint32_t)grp);  // one row per group
-    return image_bytes + 8u * (uint32_t)W * (uint32_t)sb;
-}
-
-static void* step_kernel(int W, int kind, int store_mode, int replay, int sb, int rollout, int grp) {
-    if (replay) sb = BLOCK;
-    return kind == KIND_PREDICTOR_MIX ? step_fn_w<KIND_PREDICTOR_MIX>(W, store_mode, replay, sb, rollout, grp)
-                                      : step_fn_w<KIND_PROB_TABLE>(W, store_mode, replay, sb, rollout, grp);
-}
-
-int launch_step(int W, const StepArgs& a, int store_mode, int replay, int sb, int grid, void* stream) {
-    if (replay) sb = BLOCK;
-    const bool rollout = !replay && a.T > 1;
-    const int grp = rollout && a.grp > 1 ? a.grp : 1;
-    if (grp > 1) sb = BLOCK;
-    void* fn = step_kernel(W, a.L.kind, store_mode, replay, sb, rollout, grp);
-    if (!fn) return (int)hipErrorInvalidValue;
-    const uint32_t lds = step_lds_bytes(W, replay ? a.L.bytes : a.L.plane_off, sb, grp);
-    if (lds > 64u * 1024u) {
-        hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    StepArgs c = a;
-    void* kargs[] = {&c};
-    return (int)hipLaunchKernel(fn, dim3((unsigned)grid), dim3((unsigned)sb), kargs, lds, (hipStream_t)stream);
-}
-
-#ifdef PBN_STAMPS
-}  // namespace pbn
-extern "C" int pbn_exp_stamps(void* out, size_t bytes) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(pbn::g_stamps), bytes, 0, hipMemcpyDeviceToHost);
-}
-extern "C" int pbn_exp_stamps_clear() {
-    static uint64_t z[16384 * pbn::ENV_STAMPS];
-    int rc = (int)hipMemcpyToSymbol(HIP_SYMBOL(pbn::g_stamps), z, 16384 * 8 * 8, 0, hipMemcpyHostToDevice);
-    if (!rc) rc = (int)hipMemcpyToSymbol(HIP_SYMBOL(pbn::g_env_stamps), z, sizeof z, 0, hipMemcpyHostToDevice);
-    return rc;
-}
-extern "C" int pbn_exp_env_stamps(void* out, size_t bytes) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(pbn::g_env_stamps), bytes, 0, hipMemcpyDeviceToHost);
-}
-namespace pbn {
-#endif
-
-// Advances the device-side update counter by k at the end of a captured run of step launches.
-__global__ void k_bump(uint64_t* p, uint64_t k) {
-    if (threadIdx.x == 0) p[threadIdx.x] += k;
-}
-
-int launch_bump(uint64_t* p, uint64_t k, void* stream) {
-    void* kargs[] = {(void*)&p, (void*)&k};
-    return (int)hipLaunchKernel((const void*)k_bump, dim3(1), dim3(64), kargs, 0, (hipStream_t)stream);
-}
-
-int launch_init(int W, const InitArgs& a, int grid, void* stream) {
-    InitArgs c = a;
-    return launch(init_fn(W), grid, 0, stream, &c, sizeof c);
-}
-
-int launch_flip(int W, const FlipArgs& a, int grid, void* stream) {
-    FlipArgs c = a;
-    return launch(flip_fn(W), grid, 0, stream, &c, sizeof c);
-}
-
-// Packed state words [B][W] -> one byte per node [B][N] (Graph.getState as bytes, base.py:320-324):
-// one thread per output byte, so consecutive lanes write consecutive bytes (the rows of N bytes
-// are not 4-byte aligned) and read the same few words through L1/L2.
-__global__ __launch_bounds__(BLOCK) void k_unpack(const uint64_t* __restrict__ words, uint8_t* __restrict__ out,
-                                                  uint64_t total, uint32_t N, uint32_t W) {
-    if (total <= 0xFFFFFFFFull) {  // 32-bit index math (a 64-bit divide is a long software sequence)
-        for (uint32_t k = blockIdx.x * BLOCK + threadIdx.x; k < (uint32_t)total; k += gridDim.x * BLOCK) {
-            const uint32_t e = k / N, n = k - e * N;
-            out[k] = (uint8_t)((words[(uint64_t)e * W + (n >> 6)] >> (n & 63u)) & 1u);
-        }
-        return;
-    }
-    for (uint64_t k = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; k < total; k += (uint64_t)gridDim.x * BLOCK) {
-        const uint64_t e = k / N;
-        const uint32_t n = (uint32_t)(k - e * N);
-        out[k] = (uint8_t)((words[e * W + (n >> 6)] >> (n & 63u)) & 1u);
-    }
-}
-
-int launch_unpack(const uint64_t* words, uint8_t* out, uint64_t B, uint32_t N, uint32_t W, int grid, void* stream) {
-    const uint64_t total = B * N;
-    void* kargs[] = {(void*)&words, (void*)&out, (void*)&total, (void*)&N, (void*)&W};
-    return (int)hipLaunchKernel((const void*)k_unpack, dim3((unsigned)grid), dim3(BLOCK), kargs, 0,
-                                (hipStream_t)stream);
-}
-
-int launch_env_multi(int W, const EnvArgs& a, int replay, int grid, void* stream) {
-    void* fn = a.L.kind == KIND_PREDICTOR_MIX ? env_fn_w<KIND_PREDICTOR_MIX>(W, replay, a.fast, a.grp)
-                                              : env_fn_w<KIND_PROB_TABLE>(W, replay, a.fast, a.grp);
-    EnvArgs c = a;
-    return launch(fn, grid, env_lds_bytes(W, a.L.bytes + a.erec_shift, replay ? std::min(a.fast, 1) : a.fast, a.grp,
-                                          a.L.n_nodes, a.chunk),
-                  stream, &c, sizeof c, env_block(a.fast));
-}
-
-static int occupancy(void* fn, int block, uint32_t lds, int* blocks_per_cu) {
-    int nb = 0;
-    if (lds > 64u * 1024u) {
-        hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)fn, block, lds);
-    if (e != hipSuccess) return (int)e;
-    *blocks_per_cu = nb < 1 ? 1 : nb;
-    return 0;
-}
-
-int max_blocks_step(int W, int kind, uint32_t lds_bytes, int sb, int* blocks_per_cu, int rollout, int grp) {
-    if (grp > 1) sb = BLOCK;
-    void* fn = step_kernel(W, kind, STORE_FULL, 0, sb, rollout, grp);
-    if (!fn) return (int)hipErrorInvalidValue;
-    return occupancy(fn, sb, step_lds_bytes(W, lds_bytes, sb, grp), blocks_per_cu);
+static void* env_kernel(int W, int kind, int replay, int fast, int grp) {
+    return kind == KIND_PREDICTOR_MIX ? env_fn_w<KIND_PREDICTOR_MIX>(W, replay, fast, grp)
+                                      : env_fn_w<KIND_PROB_TABLE>(W, replay, fast, grp);
 }
 
 uint32_t env_lds_bytes(int W, uint32_t image_bytes, int fast, int grp, int n_nodes, uint32_t chunk) {
@@ -2913,10 +1711,29 @@ uint32_t env_lds_bytes(int W, uint32_t image_bytes, int fast, int grp, int n_nod
     return fast == 2 || fast == 4 ? planes + (ENV_BLOCK / 64) * env_gen_wave_bytes(chunk) + (fast == 4 ? 16u : 0u) : planes;
 }
 
-int max_blocks_env(int W, int kind, int fast, int grp, uint32_t lds_bytes, int* blocks_per_cu, int n_nodes, uint32_t chunk) {
-    void* fn = kind == KIND_PREDICTOR_MIX ? env_fn_w<KIND_PREDICTOR_MIX>(W, 0, fast, grp)
-                                          : env_fn_w<KIND_PROB_TABLE>(W, 0, fast, grp);
-    return occupancy(fn, env_block(fast), env_lds_bytes(W, lds_bytes, fast, grp, n_nodes, chunk), blocks_per_cu);
+int launch_env_multi(int W, const EnvArgs& a, int replay, int grid, void* stream) {
+    EnvArgs c = a;
+    return launch(env_kernel(W, a.L.kind, replay, a.fast, a.grp), grid, env_block(a.fast),
+                  env_lds_bytes(W, a.L.bytes + a.erec_shift, replay ? std::min(a.fast, 1) : a.fast, a.grp, a.L.n_nodes,
+                                a.chunk),
+                  stream, &c);
 }
+
+int max_blocks_env(int W, int kind, int fast, int grp, uint32_t lds_bytes, int* blocks_per_cu, int n_nodes, uint32_t chunk) {
+    return occupancy(env_kernel(W, kind, 0, fast, grp), env_block(fast),
+                     env_lds_bytes(W, lds_bytes, fast, grp, n_nodes, chunk), blocks_per_cu);
+}
+
+#ifdef PBN_STAMPS
+int env_stamps_clear() {
+    static uint64_t z[16384 * ENV_STAMPS];
+    return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_env_stamps), z, sizeof z, 0, hipMemcpyHostToDevice);
+}
+}  // namespace pbn
+extern "C" int pbn_exp_env_stamps(void* out, size_t bytes) {
+    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(pbn::g_env_stamps), bytes, 0, hipMemcpyDeviceToHost);
+}
+namespace pbn {
+#endif
 
 }  // namespace pbn

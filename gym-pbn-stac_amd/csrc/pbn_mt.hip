@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "pbn_device.hpp"
+#include "pbn_launch.hpp"
 #include "pbn_params.hpp"
 
 namespace pbn {
@@ -569,32 +570,12 @@ __global__ __launch_bounds__(BLOCK) void k_mt_staged(MTArgs a) {
 
 template <bool WIDE, bool TP4>
 static void* mt_staged_fn(int W) {
-    switch (W) {
-        case 1: return (void*)k_mt_staged<1, WIDE, TP4>;
-        case 2: return (void*)k_mt_staged<2, WIDE, TP4>;
-        case 3: return (void*)k_mt_staged<3, WIDE, TP4>;
-        case 4: return (void*)k_mt_staged<4, WIDE, TP4>;
-        case 5: return (void*)k_mt_staged<5, WIDE, TP4>;
-        case 6: return (void*)k_mt_staged<6, WIDE, TP4>;
-        case 7: return (void*)k_mt_staged<7, WIDE, TP4>;
-        case 8: return (void*)k_mt_staged<8, WIDE, TP4>;
-    }
-    return nullptr;
+    return by_words<8>(W, [](auto w) { return (void*)k_mt_staged<w, WIDE, TP4>; });
 }
 
 template <int KIND, bool WIDE>
 static void* mt_step_fn(int W) {
-    switch (W) {
-        case 1: return (void*)k_mt_step<1, KIND, WIDE>;
-        case 2: return (void*)k_mt_step<2, KIND, WIDE>;
-        case 3: return (void*)k_mt_step<3, KIND, WIDE>;
-        case 4: return (void*)k_mt_step<4, KIND, WIDE>;
-        case 5: return (void*)k_mt_step<5, KIND, WIDE>;
-        case 6: return (void*)k_mt_step<6, KIND, WIDE>;
-        case 7: return (void*)k_mt_step<7, KIND, WIDE>;
-        case 8: return (void*)k_mt_step<8, KIND, WIDE>;
-    }
-    return nullptr;
+    return by_words<8>(W, [](auto w) { return (void*)k_mt_step<w, KIND, WIDE>; });
 }
 
 static bool mt_wide(const NetLayout& L) { return L.kind == KIND_PREDICTOR_MIX && L.pmax > 128u; }
@@ -603,8 +584,7 @@ int launch_mt_seed(int W, const MTArgs& a, int grid, void* stream) {
     (void)W;
     void* fn = a.L.kind == KIND_PREDICTOR_MIX ? (void*)k_mt_seed<KIND_PREDICTOR_MIX> : (void*)k_mt_seed<KIND_PROB_TABLE>;
     MTArgs c = a;
-    void* kargs[] = {&c};
-    return (int)hipLaunchKernel(fn, dim3((unsigned)grid), dim3(BLOCK), kargs, 0, (hipStream_t)stream);
+    return launch(fn, grid, BLOCK, 0, stream, &c);
 }
 
 uint32_t mt_lds_bytes(int W, const NetLayout& L) {
@@ -627,13 +607,11 @@ int launch_mt_step(int W, const MTArgs& a, int n_cu, void* stream) {
     // (staged: + one granule row after the last wave's windows, read by a lane at the end of its window)
     const uint32_t lds = mt_lds_bytes(W, a.L) + (staged ? MT_WIN * 4u * BLOCK + (MT_RING - MT_CHUNK) * entry * BLOCK + 1024u : 0u);
     int bpc = 0;
-    if (hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, reinterpret_cast<const void*>(fn), BLOCK, lds))
-        return (int)e;
+    if (int e = occupancy(fn, BLOCK, lds, &bpc)) return e;
     const uint64_t want = (a.B + BLOCK - 1) / BLOCK;
-    const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)n_cu * (uint64_t)std::max(bpc, 1)));
+    const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)n_cu * (uint64_t)bpc));
     MTArgs c = a;
-    void* kargs[] = {&c};
-    return (int)hipLaunchKernel(fn, dim3((unsigned)grid), dim3(BLOCK), kargs, lds, (hipStream_t)stream);
+    return launch(fn, grid, BLOCK, lds, stream, &c);
 }
 
 }  // namespace pbn

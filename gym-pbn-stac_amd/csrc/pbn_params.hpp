@@ -223,7 +223,7 @@ struct SyncArgs {
     uint32_t off_planes, off_gap, lds_bytes;
 };
 
-// Launchers (pbn_kernels.hip, pbn_mt.hip, pbn_ssd.hip, pbn_sync.hip). Return hipError_t as int.
+// Launchers (pbn_step.hip, pbn_state.hip, pbn_env.hip, pbn_group.hip, pbn_mt.hip, pbn_ssd.hip, pbn_sync.hip). Return hipError_t as int.
 int launch_bump(uint64_t* p, uint64_t k, void* stream);
 int launch_step(int W, const StepArgs& a, int store_mode, int replay, int sb, int grid, void* stream);
 uint32_t step_lds_bytes(int W, uint32_t image_bytes, int sb, int grp = 1);

@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include "pbn_device.hpp"
+#include "pbn_launch.hpp"
 #include "pbn_params.hpp"
 
 namespace pbn {
@@ -142,11 +143,6 @@ __global__ __launch_bounds__(SSD_WAVE_MAX_BLOCK) void k_ssd_wave(SSDArgs a) {
     uint16_t* fpos = reinterpret_cast<uint16_t*>(wb + 64 * 16);       // [64][SSD_FMAX]
     uint8_t* fcnt = wb + 64 * 16 + 64 * 2 * SSD_FMAX;                 // [64], SSD_FMAX + 1 = overflow
     const RowT R{reinterpret_cast<uint32_t*>(wb + 64 * 16 + 64 * 2 * SSD_FMAX + 64)};  // 2W dwords
-    auto wave_sync = [] {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
     const uint64_t waves = (uint64_t)gridDim.x * (BLK / 64);
     if (a.dag) {
         // Parallel in time: lane c owns iteration t0 + c of a 64-iteration chunk. All draws
@@ -442,32 +438,12 @@ __global__ __launch_bounds__(SSD_WAVE_MAX_BLOCK) void k_ssd_wave(SSDArgs a) {
 
 template <int KIND>
 static void* ssd_wave_fn(int W) {
-    switch (W) {
-        case 1: return (void*)k_ssd_wave<1, KIND>;
-        case 2: return (void*)k_ssd_wave<2, KIND>;
-        case 3: return (void*)k_ssd_wave<3, KIND>;
-        case 4: return (void*)k_ssd_wave<4, KIND>;
-        case 5: return (void*)k_ssd_wave<5, KIND>;
-        case 6: return (void*)k_ssd_wave<6, KIND>;
-        case 7: return (void*)k_ssd_wave<7, KIND>;
-        case 8: return (void*)k_ssd_wave<8, KIND>;
-    }
-    return nullptr;
+    return by_words<8>(W, [](auto w) { return (void*)k_ssd_wave<w, KIND>; });
 }
 
 template <int KIND>
 static void* ssd_fn(int W) {
-    switch (W) {
-        case 1: return (void*)k_ssd<1, KIND>;
-        case 2: return (void*)k_ssd<2, KIND>;
-        case 3: return (void*)k_ssd<3, KIND>;
-        case 4: return (void*)k_ssd<4, KIND>;
-        case 5: return (void*)k_ssd<5, KIND>;
-        case 6: return (void*)k_ssd<6, KIND>;
-        case 7: return (void*)k_ssd<7, KIND>;
-        case 8: return (void*)k_ssd<8, KIND>;
-    }
-    return nullptr;
+    return by_words<8>(W, [](auto w) { return (void*)k_ssd<w, KIND>; });
 }
 
 static uint32_t a16(uint32_t x) { return (x + 15u) & ~15u; }
@@ -489,15 +465,8 @@ int launch_ssd(int W, const SSDArgs& a, int grid, void* stream) {
     void* fn = a.wave ? (a.L.kind == KIND_PREDICTOR_MIX ? ssd_wave_fn<KIND_PREDICTOR_MIX>(W)
                                                           : ssd_wave_fn<KIND_PROB_TABLE>(W))
                       : (a.L.kind == KIND_PREDICTOR_MIX ? ssd_fn<KIND_PREDICTOR_MIX>(W) : ssd_fn<KIND_PROB_TABLE>(W));
-    if (!fn) return (int)hipErrorInvalidValue;
     SSDArgs c = a;
-    const uint32_t lds = c.lds_bytes;
-    if (lds > 64u * 1024u) {
-        hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    void* kargs[] = {&c};
-    return (int)hipLaunchKernel(fn, dim3((unsigned)grid), dim3(ssd_block(a)), kargs, lds, (hipStream_t)stream);
+    return launch(fn, grid, (int)ssd_block(a), c.lds_bytes, stream, &c);
 }
 
 }  // namespace pbn

@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include "pbn_device.hpp"
+#include "pbn_launch.hpp"
 #include "pbn_params.hpp"
 
 namespace pbn {
@@ -75,17 +76,7 @@ __global__ __launch_bounds__(BLOCK) void k_sync(SyncArgs a) {
 
 template <int KIND>
 static void* sync_fn(int W) {
-    switch (W) {
-        case 1: return (void*)k_sync<1, KIND>;
-        case 2: return (void*)k_sync<2, KIND>;
-        case 3: return (void*)k_sync<3, KIND>;
-        case 4: return (void*)k_sync<4, KIND>;
-        case 5: return (void*)k_sync<5, KIND>;
-        case 6: return (void*)k_sync<6, KIND>;
-        case 7: return (void*)k_sync<7, KIND>;
-        case 8: return (void*)k_sync<8, KIND>;
-    }
-    return nullptr;
+    return by_words<8>(W, [](auto w) { return (void*)k_sync<w, KIND>; });
 }
 
 uint32_t sync_layout(int W, uint32_t image_bytes, int n_nodes, SyncArgs* a) {
@@ -96,15 +87,8 @@ uint32_t sync_layout(int W, uint32_t image_bytes, int n_nodes, SyncArgs* a) {
 
 int launch_sync(int W, const SyncArgs& a, int grid, void* stream) {
     void* fn = a.L.kind == KIND_PREDICTOR_MIX ? sync_fn<KIND_PREDICTOR_MIX>(W) : sync_fn<KIND_PROB_TABLE>(W);
-    if (!fn) return (int)hipErrorInvalidValue;
     SyncArgs c = a;
-    if (c.lds_bytes > 64u * 1024u) {
-        hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)c.lds_bytes);
-        if (e != hipSuccess) return (int)e;
-    }
-    void* kargs[] = {&c};
-    return (int)hipLaunchKernel(fn, dim3((unsigned)grid), dim3(BLOCK), kargs, c.lds_bytes, (hipStream_t)stream);
+    return launch(fn, grid, BLOCK, c.lds_bytes, stream, &c);
 }
 
 }  // namespace pbn

@@ -1,4 +1,4 @@
-"""The tail session's Philox split (pbn_kernels.hip, k_env tail mode, the draw lambda): the 64 calls of a
+"""The tail session's Philox split (pbn_env.hip, k_env tail mode, the draw lambda): the 64 calls of a
 block differ in counter word 0 only (words 1-3 are the session's call index and env id), so half of
 rounds 0 and 1 is computed once per session and a call does 18 multiplies instead of 20. Restated
 here in Python integers and checked against the oracle's Philox4x32-10 (Random123 KAT-checked in

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Loops of one kernel in a `make asm` listing: for every backward branch, the loop's line span, its
 instruction count and its scratch (spill) loads/stores -- to see whether spills sit on a hot loop.
-Measurement tooling only. Usage: python tools/asm_loops.py LISTING.s SYMBOL [min_instrs]"""
+Measurement tooling only. Usage: python tools/asm_loops.py LISTING.s SYMBOL [min_instrs]
+(`make asm` writes one listing per kernel file: gym-pbn-stac_amd/build/asm/pbn_env/pbn_env-hip-amdgcn-amd-amdhsa-gfx950.s
+holds k_env, .../pbn_step/... k_step, and so on)"""
 import re
 import sys
 
