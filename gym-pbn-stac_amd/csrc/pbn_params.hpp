@@ -223,7 +223,53 @@ struct SyncArgs {
     uint32_t off_planes, off_gap, lds_bytes;
 };
 
-// Launchers (pbn_step.hip, pbn_state.hip, pbn_env.hip, pbn_group.hip, pbn_mt.hip, pbn_ssd.hip, pbn_sync.hip). Return hipError_t as int.
+// Attractor discovery (pbn_reach.hip): an exact device set of packed states plus the support-graph kernels
+// that grow it (forward closure) and mark inside it (backward reachability). DESIGN.md §11.
+//   keys   [key_cap][W]; entry e is live once a table slot points at it, dead (mark REACH_DEAD) if its
+//          inserter lost the publish to an equal key or could not place it. A dead entry goes onto the free
+//          ring and is handed out again from the next BFS level on.
+//   table  open addressing, [tmask + 1] u64: 0 = empty, else hash tag << 32 | entry + 1; written once (CAS)
+//   queue  [key_cap] entry indices: every publish (forward) or mark (backward) appends one; a frontier is a
+//          range of it
+//   ctl    REACH_CTL_WORDS u32 counters, see the enum
+enum {
+    REACH_KEYS = 0,       // entries taken from the end of keys (may run past key_cap: the host clamps)
+    REACH_COUNT = 1,      // live entries: successful publishes
+    REACH_OVERFLOW = 2,   // an insert found max_states entries, a full key array or a full table
+    REACH_QTAIL = 3,      // queue: entries appended
+    REACH_MISSING = 4,    // mark_backward: the start state is not in the set
+    REACH_FREE_HEAD = 5,  // free ring: entries taken (may run past the level's limit: the host clamps)
+    REACH_FREE_TAIL = 6,  // free ring: entries pushed
+    REACH_CTL_WORDS = 8
+};
+constexpr uint32_t REACH_NONE = 0xFFFFFFFFu;
+constexpr uint32_t REACH_DEAD = 0x80000000u;     // mark of a dead entry (epochs stay below it)
+constexpr uint32_t REACH_CHUNK = 16384;          // frontier entries per launch (short launches; a level takes several)
+constexpr uint32_t REACH_MAX_GRID = 2048;        // workgroups per launch (4 waves each; a wave walks its entries)
+
+struct ReachArgs {
+    const void* img;             // network image (predictor mix)
+    NetLayout L;
+    uint64_t* keys;
+    uint32_t* mark;              // [key_cap] epoch of the last mark_backward that reached the entry, or REACH_DEAD
+    unsigned long long* table;
+    uint32_t* ctl;
+    uint32_t* queue;
+    uint32_t* free_ring;         // [fmask + 1] dead entries, positions REACH_FREE_HEAD .. REACH_FREE_TAIL
+    unsigned long long* hull;    // [2][W]: AND, OR over the live entries
+    const uint64_t* in;          // unstable / seed / mark start: states [n_in][W]
+    uint64_t* out;               // unstable: masks [n_in][W]
+    uint64_t n_in;
+    uint32_t tmask, key_cap, max_states, fmask;
+    uint32_t free_limit;         // ring positions below this were pushed by earlier levels: safe to take
+    uint32_t free_any;           // 0: nothing to take in this level (skip the counter)
+    uint32_t lo, hi;             // this launch's slice of the queue (hull: of keys)
+    uint32_t epoch;
+};
+
+// Launchers (pbn_step.hip, pbn_state.hip, pbn_env.hip, pbn_group.hip, pbn_mt.hip, pbn_ssd.hip, pbn_sync.hip, pbn_reach.hip). Return hipError_t as int.
+enum { REACH_K_UNSTABLE = 0, REACH_K_SEED, REACH_K_EXPAND, REACH_K_BACK_START, REACH_K_BACK, REACH_K_HULL };
+int launch_reach(int W, int which, const ReachArgs& a, int grid, void* stream);
 int launch_bump(uint64_t* p, uint64_t k, void* stream);
 int launch_step(int W, const StepArgs& a, int store_mode, int replay, int sb, int grid, void* stream);
 uint32_t step_lds_bytes(int W, uint32_t image_bytes, int sb, int grp = 1);

@@ -30,6 +30,10 @@ def __getattr__(name):
         from . import envs
 
         return getattr(envs, name)
+    if name in ("find_attractors", "AttractorResult", "ReachSet", "cube_cover"):
+        from . import attractors
+
+        return getattr(attractors, name)
     if name == "make":
         from .registry import make
 

@@ -77,6 +77,14 @@ class EnvCfgDesc(C.Structure):
     ]
 
 
+class ReachInfo(C.Structure):
+    _fields_ = [
+        ("n_nodes", C.c_int32), ("n_words", C.c_int32), ("device", C.c_int32), ("complete", C.c_int32),
+        ("max_states", C.c_uint64), ("table_slots", C.c_uint64), ("key_capacity", C.c_uint64),
+        ("n_states", C.c_uint64), ("n_entries", C.c_uint64),
+    ]
+
+
 _PP = C.POINTER(_vp)
 
 # name -> (restype, argtypes); mirrors include/pbn_abi.h one to one
@@ -130,6 +138,14 @@ SIGNATURES = {
     "pbn_env_tail_helpers": (C.c_int, [_vp, _u32p]),
     "pbn_env_tail_stats": (C.c_int, [_vp, _u32p]),
     "pbn_env_grid_stats": (C.c_int, [_vp, _u32p]),
+    "pbn_reach_create": (C.c_int, [_vp, C.c_int, C.c_uint64, _PP]),
+    "pbn_reach_destroy": (None, [_vp]),
+    "pbn_reach_get_info": (C.c_int, [_vp, C.POINTER(ReachInfo)]),
+    "pbn_reach_unstable": (C.c_int, [_vp, _u64p, C.c_uint64, _u64p]),
+    "pbn_reach_closure": (C.c_int, [_vp, _u64p, C.c_uint64, _u64p, _i32p]),
+    "pbn_reach_mark_backward": (C.c_int, [_vp, _u64p, _u64p]),
+    "pbn_reach_read": (C.c_int, [_vp, _u64p, _u32p, C.c_uint64, _u64p]),
+    "pbn_reach_hull": (C.c_int, [_vp, _u64p, _u64p]),
 }
 
 

@@ -23,6 +23,7 @@ import numpy as np
 
 from . import spaces
 from . import _lib as L
+from .attractors import resolve_all_attractors
 from .batch import EnvConfig, Net, PBNBatch, pack_bits, unpack_bits
 from .network import PredictorNetwork, TruthTableNetwork, load_network
 
@@ -247,6 +248,8 @@ class VecPBNTargetMultiEnv:
         self.net = net
         self.num_envs = int(n_envs)
         self.N = net.n_nodes
+        # "find": discovered on the device (gym_pbn_amd.attractors), opt-in
+        attractors = resolve_all_attractors(net, attractors, device=device, seed=seed)
         self.cfg = EnvConfig(net, attractors, horizon=horizon)
         self.batch = PBNBatch(net, n_envs, device=device, env_id_base=env_id_base, seed=seed)
         self.update_cap = int(update_cap)
@@ -276,8 +279,12 @@ class VecPBNTargetMultiEnv:
 class PBNTargetMultiEnv:
     """Single-env mirror of ``PBNTargetMultiEnv`` with ``BittnerMulti7`` attractor handling."""
 
-    def __init__(self, network, attractors, horizon: int = 100, device: int = 0, seed: int = 0,
-                 update_cap: int = 1 << 20, name: Optional[str] = None):
+    def __init__(self, network, attractors=None, horizon: int = 100, device: int = 0, seed: int = 0,
+                 update_cap: int = 1 << 20, name: Optional[str] = None, *, all_attractors=None):
+        if attractors is None:
+            attractors = all_attractors  # the reference's name for the same list; "find" = discover them
+        if attractors is None:
+            raise ValueError("all_attractors is required (cabean output, or \"find\"; see gym_pbn_amd.io.cabean)")
         if not isinstance(network, PredictorNetwork):
             network = load_network(network)
         self.network = network
@@ -343,6 +350,7 @@ class PBNTargetEnv:
 
     def __init__(self, network, all_attractors, horizon: int = 100, device: int = 0, seed: int = 0,
                  update_cap: int = 1 << 20, name: Optional[str] = None):
+        all_attractors = resolve_all_attractors(network, all_attractors, device=device, seed=seed)  # "find"
         self.graph = Graph(network, device=device, seed=seed)
         self.N = self.graph.N
         self.name = name or self.graph.network.name

@@ -5,7 +5,9 @@ Networks the reference builds from ``genedata.xls`` by predictor inference
 (``bittner/utils.py:54-91``) are the exported networks bundled in ``gym_pbn_amd/data``
 where the reference ships their predictor sets; attractors (the reference runs the
 external ``cabean`` binary, ``get_attractors_from_cabean.py:39-54``) must be passed as
-``all_attractors`` (``gym_pbn_amd.io.cabean.attractors_list`` parses cabean's output).
+``all_attractors`` (``gym_pbn_amd.io.cabean.attractors_list`` parses cabean's output), or
+``all_attractors="find"`` has :func:`gym_pbn_amd.attractors.find_attractors` discover them on the
+device (opt-in; ``None`` still raises).
 ``max_episode_steps=100`` (a gymnasium TimeLimit in the reference) is the envs'
 ``horizon``.
 """
@@ -16,6 +18,9 @@ from typing import Callable, Dict
 
 from . import envs, mdp
 
+_REQUIRED = ("all_attractors is required (cabean output; see gym_pbn_amd.io.cabean), or all_attractors=\"find\" to "
+             "discover them on the device (gym_pbn_amd.attractors)")
+
 # id -> (factory, default kwargs). Bittner ids map to the bundled network of that size.
 _BITTNER = {28: "bittner28", 70: "bittner70", 100: "bittner100", 200: "bittner199"}
 
@@ -23,7 +28,7 @@ _BITTNER = {28: "bittner28", 70: "bittner70", 100: "bittner100", 200: "bittner19
 def _target(n):
     def f(all_attractors=None, **kw):
         if all_attractors is None:
-            raise ValueError("all_attractors is required (cabean output; see gym_pbn_amd.io.cabean)")
+            raise ValueError(_REQUIRED)
         return envs.PBNTargetEnv(kw.pop("network", _BITTNER[n]), all_attractors, **kw)
 
     return f
@@ -32,7 +37,7 @@ def _target(n):
 def _multi(n):
     def f(all_attractors=None, **kw):
         if all_attractors is None:
-            raise ValueError("all_attractors is required (cabean output; see gym_pbn_amd.io.cabean)")
+            raise ValueError(_REQUIRED)
         return envs.PBNTargetMultiEnv(kw.pop("network", _BITTNER[n]), all_attractors, **kw)
 
     return f
@@ -55,7 +60,7 @@ def _general(N=200, all_attractors=None, **kw):  # pbn_target_multi.py:531-536 (
     if net is None:
         raise NotImplementedError(f"BittnerMultiGeneral(N={N}): only N=200 ships (predictor_sets_200_5_kmeans)")
     if all_attractors is None:
-        raise ValueError("all_attractors is required (cabean output; see gym_pbn_amd.io.cabean)")
+        raise ValueError(_REQUIRED)
     return envs.PBNTargetMultiEnv(net, all_attractors, **kw)
 
 
@@ -83,7 +88,7 @@ def _pbn_target(graph=None, goal_config=None, render_mode=None, render_no_cache=
     goal = (goal_config["target_nodes"], goal_config["target_node_values"],
             goal_config["undesired_node_values"], goal_config["intervene_on"])
     if all_attractors is None:
-        raise ValueError("all_attractors is required (cabean output; see gym_pbn_amd.io.cabean)")
+        raise ValueError(_REQUIRED)
     env = envs.PBNTargetEnv(graph, all_attractors, horizon=goal_config.get("horizon", 100), name=name, **kw)
     env.target_nodes, env.target_node_values, env.undesired_node_values, env.intervene_on = goal
     env.successful_reward = reward_config["successful_reward"]

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define PBN_ABI_VERSION 14
+#define PBN_ABI_VERSION 15
 
 enum {
     PBN_OK = 0,
@@ -51,6 +51,7 @@ enum { PBN_KIND_PREDICTOR_MIX = 1, PBN_KIND_PROB_TABLE = 2 };
 typedef struct pbn_net pbn_net;
 typedef struct pbn_batch pbn_batch;
 typedef struct pbn_envcfg pbn_envcfg;
+typedef struct pbn_reach pbn_reach;
 
 /* Network tables (see gym_pbn_amd/network.py for how they are derived).
  * PREDICTOR_MIX replaces base.Node.predictors (base.py:30-45) + Predstep (:89-119):
@@ -282,6 +283,49 @@ int pbn_env_tail_stats(pbn_batch *b, uint32_t *stats);
  * wait drops the env it waited for: host-path env calls return PBN_E_HIP at once, device-path launches
  * (pbn_env_step_multi_device, pbn_env_rollout_multi_device) at the next pbn_sync. */
 int pbn_env_grid_stats(pbn_batch *b, uint32_t *stats);
+
+/* ---- attractor discovery: Graph.getNextStates / genSTG (base.py:221-242) + findAttractors (base.py:398-399) ----
+ * The reference enumerates all 2^N states on the host ("too big for PBN > 10") and otherwise shells out to the
+ * cabean binary. Here a pbn_reach is an exact set of packed states on the device, grown by reachability in the
+ * SUPPORT GRAPH of a predictor-mix network: x -> x ^ (1 << i) iff some live predictor of node i outputs 1 - x_i at
+ * x (getNextStates keeps an edge when prob > 0). A predictor is live iff its selection interval on the 53-bit
+ * grid is non-empty (pred_thr, the last threshold taken as 2^53) -- the rule is defined on the 53-bit thresholds,
+ * not on the Philox stream's 32-bit choice grid. An attractor is a terminal strongly connected component
+ * (nx.attracting_components on the reference's STG); gym_pbn_amd/attractors.py finds them with these calls.
+ * One pbn_reach = one device + one HIP stream; calls on it are synchronous and must be serialised by the caller. */
+#define PBN_REACH_MAX_STATES ((uint64_t)1 << 28)
+typedef struct {
+    int32_t n_nodes, n_words, device;
+    int32_t complete;      /* last closure: 1 = fixed point reached, 0 = it stopped at capacity */
+    uint64_t max_states;   /* live states the set accepts */
+    uint64_t table_slots;  /* open-addressing slots: the power of two >= 2 * max_states (>= 64) */
+    uint64_t key_capacity; /* key entries, live and dead (an entry that lost a publish race is dead until a later
+                              BFS level takes it again) */
+    uint64_t n_states;     /* live states */
+    uint64_t n_entries;    /* key entries in use */
+} pbn_reach_info;
+/* PROB_TABLE networks: PBN_E_UNSUPPORTED (gym_pbn_amd/stg.py is their route). device < 0: PBN_E_RANGE. */
+int pbn_reach_create(const pbn_net *net, int device, uint64_t max_states, pbn_reach **out);
+void pbn_reach_destroy(pbn_reach *r);
+int pbn_reach_get_info(const pbn_reach *r, pbn_reach_info *info);
+/* The edge rule alone (base.py:221-242, one state's row of getNextStates): host states [S][W] -> masks [S][W], bit i
+ * set iff node i can flip at that state. Does not touch the set. */
+int pbn_reach_unstable(pbn_reach *r, const uint64_t *states, uint64_t n_states, uint64_t *masks);
+/* genSTG restricted to what the seeds reach (base.py:221-242): clears the set, inserts seeds [S][W] and expands to
+ * the fixed point, one launch sequence per BFS level. *count = states in the set; *complete = 0 when max_states (or
+ * the key array) was reached first -- a normal return (PBN_OK), the set then holds the states seen so far. */
+int pbn_reach_closure(pbn_reach *r, const uint64_t *seeds, uint64_t n_seeds, uint64_t *count, int32_t *complete);
+/* Marks every state of the set that reaches `state` [W] inside the set (backward BFS over the same edges; with a
+ * complete closure F of s, |marked| == |F| iff F is an attractor, findAttractors base.py:398-399). Earlier marks
+ * are dropped. `state` not in the set: PBN_E_INVALID. *n_marked counts `state` itself. */
+int pbn_reach_mark_backward(pbn_reach *r, const uint64_t *state, uint64_t *n_marked);
+/* Read-back (base.py:398-399 returns the components as state lists): states [n][W] and marks [n] (1 = marked by the
+ * last pbn_reach_mark_backward), in an order that stays fixed until the next closure; either may be NULL. capacity = rows the arrays hold; both NULL
+ * just returns *n_states. */
+int pbn_reach_read(pbn_reach *r, uint64_t *states, uint32_t *marks, uint64_t capacity, uint64_t *n_states);
+/* Hull cube of the set (base.py:398-399's components as one cabean-style cube): all_words / any_words [W] = AND / OR
+ * over all states; node i is fixed in the hull iff bit i of all ^ any is 0. Valid for an incomplete closure too. */
+int pbn_reach_hull(pbn_reach *r, uint64_t *all_words, uint64_t *any_words);
 
 #ifdef __cplusplus
 }

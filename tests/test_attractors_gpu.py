@@ -1,0 +1,334 @@
+"""Attractor discovery on the device: the edge-rule kernel, the state set, the descent, the env switch.
+
+The independent statement of the edge rule is ``np_unstable`` in ``test_attractors_host.py``;
+golden attractors come from the reference's own ``getNextStates`` + ``findAttractors``
+(``tests/golden/attractors_small.json``).
+"""
+
+import numpy as np
+import pytest
+
+from test_attractors_host import (CASES, all_states, case_attractors, case_id, case_network, embed_network,
+                                  lift_states, np_closure, np_successors, np_unstable_words)
+
+pytestmark = pytest.mark.gpu
+
+SMALL = 1 << 13  # max_states for the golden nets (N <= 12)
+
+
+def random_states(n_nodes, count, seed):
+    from gym_pbn_amd.batch import pack_bits
+
+    return pack_bits(np.random.default_rng(seed).integers(0, 2, size=(count, n_nodes), dtype=np.uint8))
+
+
+def case_by(n, max_preds, seed):
+    return next(c for c in CASES if (c["n_nodes"], c["max_preds"], c["seed"]) == (n, max_preds, seed))
+
+
+# ---------------------------------------------------------------- unstable against the numpy rule
+@pytest.mark.parametrize("c", CASES, ids=case_id)
+def test_unstable_golden_nets(c):
+    from gym_pbn_amd.attractors import ReachSet
+
+    net = case_network(c)
+    states = all_states(c["n_nodes"])
+    assert np.array_equal(ReachSet(net, 64).unstable(states), np_unstable_words(net, states))
+
+
+@pytest.mark.parametrize("name,count", [("bittner70", 300), ("bittner199", 257)])
+def test_unstable_bundled_nets(name, count):
+    """W = 2 and W = 4; 257 states: an odd tail and more than one workgroup."""
+    from gym_pbn_amd.attractors import ReachSet
+    from gym_pbn_amd.network import load_network
+
+    net = load_network(name)
+    states = random_states(net.n_nodes, count, 3)
+    got = ReachSet(net, 64).unstable(states)
+    assert got.shape == (count, net.n_words)
+    assert np.array_equal(got, np_unstable_words(net, states))
+
+
+@pytest.mark.parametrize("n_total", [64, 65])
+def test_unstable_embedded_across_the_word_boundary(n_total):
+    """A golden N = 10 net inside 64 / 65 nodes, its nodes ending at bit 63 / straddling bits 63 and 64."""
+    from gym_pbn_amd.attractors import ReachSet
+
+    c = case_by(10, 2, 0)
+    small = case_network(c)
+    place = list(range(n_total - 10, n_total))
+    big = embed_network(small, n_total, place)
+    frozen = np.random.default_rng(5).integers(0, 2, size=n_total, dtype=np.uint8)
+    states = lift_states(all_states(10), 10, n_total, place, frozen)
+    got = ReachSet(big, 64).unstable(states)
+    assert np.array_equal(got, np_unstable_words(big, states))
+    # and it is the small net's answer moved to the new positions: frozen nodes never flip
+    want = lift_states(np_unstable_words(small, all_states(10)), 10, n_total, place, np.zeros(n_total, np.uint8))
+    assert np.array_equal(got, want)
+
+
+# ---------------------------------------------------------------- golden nets end to end
+@pytest.mark.parametrize("c", CASES, ids=case_id)
+def test_golden_attractors_from_all_states(c):
+    from gym_pbn_amd.attractors import find_attractors
+
+    net = case_network(c)
+    res = find_attractors(net, states=all_states(c["n_nodes"]), max_states=SMALL)
+    want = sorted(case_attractors(c), key=lambda a: (len(a), int(a[0, 0])))
+    assert not res.incomplete
+    assert [len(a) for a in res.attractors] == [len(a) for a in want]
+    for got, w in zip(res.attractors, want):
+        assert np.array_equal(got, w)
+    assert sum(res.seed_counts) == 1 << c["n_nodes"]  # transient seeds included: they went through the descent
+    assert all(n >= len(a) for n, a in zip(res.seed_counts, res.attractors))
+
+
+def test_descent_from_single_transient_seeds():
+    """One seed at a time (no joint closure): a transient seed descends to an attractor it reaches."""
+    from gym_pbn_amd.attractors import find_attractors, rows_in
+
+    c = case_by(12, 3, 1)
+    net = case_network(c)
+    golden = case_attractors(c)
+    inside = np.zeros(1 << 12, dtype=bool)
+    for a in golden:
+        inside[a[:, 0].astype(np.int64)] = True
+    transient = np.flatnonzero(~inside).astype(np.uint64)
+    for s in transient[:: len(transient) // 5][:5]:
+        res = find_attractors(net, states=np.array([[s]], np.uint64), max_states=SMALL)
+        assert len(res.attractors) == 1 and res.seed_counts == [1] and not res.incomplete
+        assert any(np.array_equal(res.attractors[0], a) for a in golden)
+        assert rows_in(res.attractors[0][:1], np_closure(net, np.array([[s]], np.uint64)))[0]
+
+
+def test_per_seed_path_merges_seeds_of_one_attractor():
+    """Several transient seeds whose joint closure does not fit ``max_states`` while each single one does:
+    the per-seed path. Seeds that descend to the same attractor share one entry."""
+    from gym_pbn_amd.attractors import find_attractors, rows_in
+
+    c = case_by(12, 3, 1)
+    net = case_network(c)
+    golden = sorted(case_attractors(c), key=lambda a: (len(a), int(a[0, 0])))
+    inside = np.zeros(1 << 12, dtype=bool)
+    for a in golden:
+        inside[a[:, 0].astype(np.int64)] = True
+    transient = np.flatnonzero(~inside).astype(np.uint64)
+    cap = 1024
+    seeds, reaches = [], []
+    for s in transient[:: len(transient) // 24][:24]:
+        cl = np_closure(net, np.array([[s]], np.uint64))
+        if len(cl) <= cap:
+            seeds.append(s)
+            reaches.append([bool(rows_in(a[:1], cl)[0]) for a in golden])
+    seeds = np.array(seeds, np.uint64).reshape(-1, 1)
+    reaches = np.array(reaches)
+    assert len(seeds) >= 10 and len(np_closure(net, seeds)) > cap  # the joint closure does not fit
+    assert (reaches.sum(axis=1) == 1).any() and reaches[reaches.sum(axis=1) == 1].any(axis=0).all()
+    res = find_attractors(net, states=seeds, max_states=cap)
+    assert not res.incomplete
+    assert len(res.attractors) == len(golden)  # no attractor listed twice
+    for got, want in zip(res.attractors, golden):
+        assert np.array_equal(got, want)
+    assert sum(res.seed_counts) == len(seeds)
+    for j, n in enumerate(res.seed_counts):  # a seed counts for an attractor it reaches
+        only = int((reaches[:, j] & (reaches.sum(axis=1) == 1)).sum())
+        assert only <= n <= int(reaches[:, j].sum())
+
+
+# ---------------------------------------------------------------- W = 4 closure
+def test_closure_four_words_matches_embedded_network():
+    from gym_pbn_amd.attractors import ReachSet, sort_rows
+    from gym_pbn_amd.batch import PBNBatch
+    from gym_pbn_amd.network import load_network
+
+    small = load_network("bittner28")
+    place = np.sort(np.random.default_rng(11).choice(199, size=28, replace=False))
+    place[[0, -1]] = [1, 198]
+    assert set(place // 64) == {0, 1, 2, 3}  # live nodes in all four words
+    big = embed_network(small, 199, place)
+    b = PBNBatch(small, 1, seed=4)
+    b.randomize()
+    b.rollout(64 * 28)
+    seed = b.get_state()
+    rs = ReachSet(small, 1 << 17)
+    n, complete = rs.closure(seed)
+    assert complete and n >= 2
+    inner = sort_rows(rs.read()[0])
+    frozen = np.random.default_rng(12).integers(0, 2, size=199, dtype=np.uint8)
+    rb = ReachSet(big, 1 << 17)
+    nb, complete_b = rb.closure(lift_states(seed, 28, 199, place, frozen))
+    assert complete_b and nb == n
+    assert np.array_equal(sort_rows(rb.read()[0]), sort_rows(lift_states(inner, 28, 199, place, frozen)))
+    a, o = rb.hull()
+    assert np.array_equal(a, np.bitwise_and.reduce(rb.read()[0], axis=0))
+    assert np.array_equal(o, np.bitwise_or.reduce(rb.read()[0], axis=0))
+
+
+# ---------------------------------------------------------------- capacity
+def test_capacity_is_a_normal_return():
+    from gym_pbn_amd.attractors import ReachSet, find_attractors, hull_cube, rows_in
+
+    c = case_by(10, 2, 4)
+    net = case_network(c)
+    att = case_attractors(c)[0]
+    K = len(att)
+    assert K == 640
+    seed = att[:1]
+    rs = ReachSet(net, K)
+    assert rs.closure(seed) == (K, True)
+    assert rs.mark_backward(seed) == K
+    states, marks = rs.read()
+    assert len(states) == K and marks.all()
+
+    rs = ReachSet(net, K - 1)
+    n, complete = rs.closure(seed)
+    assert not complete and n >= 1
+    assert rs.info()["complete"] == 0
+    states, _ = rs.read()
+    assert len(states) == n and len(np.unique(states, axis=0)) == n
+    assert (states[:, 0] == seed[0, 0]).any()
+    assert rows_in(states, att).all()  # what it holds is part of the closure
+    a, o = rs.hull()
+    assert np.array_equal(a, np.bitwise_and.reduce(states, axis=0))
+    assert np.array_equal(o, np.bitwise_or.reduce(states, axis=0))
+
+    res = find_attractors(net, states=seed, max_states=K - 1)
+    assert not res.attractors and len(res.incomplete) == 1
+    e = res.incomplete[0]
+    assert e["n_seeds"] == 1 and e["n_seen"] >= 1
+    assert len(e["hull"]) == 10 and "*" in e["hull"]
+    full = hull_cube(np.bitwise_and.reduce(att, axis=0), np.bitwise_or.reduce(att, axis=0), 10)
+    assert all(h == f or f == "*" for h, f in zip(e["hull"], full))  # inside the full closure's hull
+
+
+def test_set_at_maximum_load_factor():
+    """max_states a power of two: the table has exactly 2 * max_states slots and fills to one half."""
+    from gym_pbn_amd.attractors import ReachSet, sort_rows
+
+    c = case_by(10, 2, 0)
+    att = case_attractors(c)[-1]
+    assert len(att) == 128
+    rs = ReachSet(case_network(c), 128)
+    assert rs.closure(att[:1]) == (128, True)
+    info = rs.info()
+    assert info["table_slots"] == 256 and info["n_states"] * 2 == info["table_slots"]
+    assert np.array_equal(sort_rows(rs.read()[0]), att)
+    # all 128 given as seeds at once: same set, nothing to expand
+    assert rs.closure(att) == (128, True)
+    assert np.array_equal(sort_rows(rs.read()[0]), att)
+
+
+def test_refusals():
+    from gym_pbn_amd import _lib as L
+    from gym_pbn_amd.attractors import ReachSet
+    from gym_pbn_amd.network import load_network
+
+    with pytest.raises(L.PbnError) as e:
+        ReachSet(load_network("tt8"), 64)
+    assert e.value.code == L.PBN_E_UNSUPPORTED
+    with pytest.raises(ValueError):
+        ReachSet("bittner28", 64, device=-1)
+    c = case_by(10, 2, 8)
+    att = case_attractors(c)[0]  # two states
+    rs = ReachSet(case_network(c), 64)
+    with pytest.raises(L.PbnError) as e:
+        rs.mark_backward(att[:1])  # nothing in the set yet
+    assert e.value.code == L.PBN_E_STATE
+    assert rs.closure(att[:1]) == (2, True)
+    outside = np.array([[next(v for v in range(1 << 10) if v not in att[:, 0])]], np.uint64)
+    with pytest.raises(ValueError):
+        rs.mark_backward(outside)  # not a member of the set
+    assert rs.mark_backward(att[1:]) == 2  # and the set is still usable
+    with pytest.raises(ValueError):
+        rs.closure(np.array([[1 << 10]], np.uint64))  # a bit past the last node
+
+
+# ---------------------------------------------------------------- the bundled networks
+def check_attractor(net, att):
+    """Closed: every successor is a member. Strongly connected: one strong component."""
+    from scipy.sparse import coo_matrix
+    from scipy.sparse.csgraph import connected_components
+
+    from gym_pbn_amd.attractors import _row_keys
+
+    keys = _row_keys(att)
+    order = np.argsort(keys)
+    src, succ = np_successors(net, att)
+    sk = _row_keys(succ)
+    pos = np.searchsorted(keys[order], sk)
+    pos[pos == len(att)] = 0
+    assert (keys[order][pos] == sk).all(), "a successor leaves the set"
+    dst = order[pos]
+    g = coo_matrix((np.ones(len(src), np.int8), (src, dst)), shape=(len(att), len(att))).tocsr()
+    assert connected_components(g, directed=True, connection="strong")[0] == 1
+
+
+@pytest.mark.parametrize("name,n_seeds", [("bittner28", 64), ("bittner70", 16)])
+def test_bundled_networks_end_to_end(name, n_seeds):
+    from gym_pbn_amd.attractors import find_attractors
+    from gym_pbn_amd.network import load_network
+
+    net = load_network(name)
+    # bittner70 has a 2^17- and a 2^19-state attractor; 2^18 keeps the host-side check of every returned state
+    # short, and seeds that end in the larger one must then come back as incomplete
+    res = find_attractors(net, n_seeds=n_seeds, max_states=1 << 18, seed=1)
+    print(name, "attractor sizes", [len(a) for a in res.attractors], "seed counts", res.seed_counts,
+          "incomplete", [(e["n_seen"], e["n_seeds"]) for e in res.incomplete])
+    # a seed still transient after the burn-in may have a closure past max_states: reported, never guessed
+    assert res.attractors
+    assert sum(res.seed_counts) + sum(e["n_seeds"] for e in res.incomplete) == n_seeds
+    for a in res.attractors:
+        assert len(np.unique(a, axis=0)) == len(a)
+        check_attractor(net, a)
+    from gym_pbn_amd.attractors import rows_in
+
+    for j, a in enumerate(res.attractors):  # pairwise disjoint, hence no repeats
+        for b in res.attractors[j + 1:]:
+            assert not rows_in(a, b).any()
+    if name == "bittner70":  # middle levels of a 2^17-state cube (24,310 states) take more than one launch
+        assert max(len(a) for a in res.attractors) > 65536
+    cubes = res.all_attractors()
+    assert len(cubes) == len(res.attractors)
+
+
+def test_bittner199_is_reported_incomplete():
+    from gym_pbn_amd.attractors import find_attractors
+    from gym_pbn_amd.batch import PBNBatch
+
+    res = find_attractors("bittner199", n_seeds=4, max_states=1 << 16, seed=2)
+    assert not res.attractors and res.seed_counts == []
+    assert res.incomplete and sum(e["n_seeds"] for e in res.incomplete) == 4
+    for e in res.incomplete:
+        assert e["n_seen"] >= 1 << 16
+        assert len(e["hull"]) == 199 and e["hull"].count("*") >= 16
+    b = PBNBatch("bittner199", 64, seed=1)  # the device is fine afterwards
+    b.randomize()
+    b.rollout(16)
+    b.sync()
+
+
+def test_env_from_found_attractors():
+    from gym_pbn_amd.envs import PBNTargetMultiEnv, _cube_match
+
+    env = PBNTargetMultiEnv("bittner28", all_attractors="find")
+    cubes = [c for a in env.all_attractors for c in a]
+    assert cubes and all(len(c) == 28 for c in cubes)
+    (obs, _), _ = env.reset()
+    assert any(_cube_match(c, obs) for c in env.all_attractors[0])
+    rng = np.random.default_rng(0)
+    for _ in range(20):
+        obs, _, _, _, _ = env.step([int(rng.integers(0, 29))])
+        assert any(_cube_match(c, obs) for c in cubes)
+
+
+def test_target_env_from_found_attractors():
+    """``PBNTargetEnv`` (the ``Bittner-28-v0`` id) with a network name handed to the discovery."""
+    from gym_pbn_amd.envs import _cube_match
+    from gym_pbn_amd.registry import make
+
+    env = make("gym-PBN/Bittner-28-v0", all_attractors="find")
+    assert len(env.all_attractors) >= 2 and all(len(c) == 28 for a in env.all_attractors for c in a)
+    (state, target), _ = env.reset(seed=3)
+    assert any(_cube_match(c, state) for c in env.cubes) and any(_cube_match(c, target) for c in env.target)
+    obs, _, _, _, _ = env.step(0, force=False)
+    assert env.is_attracting_state(obs)
