@@ -1,0 +1,422 @@
+// pbn_abi_sim.cpp -- everything that advances a plain batch: step mode and its HIP graphs, rollout,
+// replay / forced updates, MT mode, the synchronous step and the SSD histogram.
+// step_launch stays next to pbn_step and the graph capture: single-env and small-batch stepping are
+// launch-bound on the host.
+#include "pbn_host.hpp"
+
+static int step_launch(pbn_batch* b, uint32_t T, uint64_t update_base, int replay, const void* d_i, const void* d_k,
+                       const uint64_t* ubase_dev = nullptr, bool timed = true) {
+    StepArgs a{};
+    a.ubase_dev = ubase_dev;
+    a.state = b->d_state;
+    a.img = b->d_image;
+    a.L = b->net->L;
+    a.B = b->B;
+    a.env_base = b->env_base;
+    a.seed = b->seed;
+    a.update_base = update_base;
+    a.T = T;
+    a.replay_node = (const uint32_t*)d_i;
+    a.replay_k53 = (const uint64_t*)d_k;
+    hipEvent_t stop = nullptr;
+    if (timed)
+        if (int rc = b->ev_begin(&stop)) return rc;
+    int store = (T == 1 && !replay) ? b->knob.store_mode : STORE_FULL;
+    // step mode: K envs per thread (their loads overlap); rollout: one env per lane up to the
+    // resident grid -- its T updates are the work, and more lanes hide more LDS latency
+    // (Bittner-28 @65,536 envs, T = 256: 115 vs 62 G updates/s with K = 2)
+    const bool rollout = T > 1 && !replay;  // k_rollout (or k_rollout_grp), 256-thread groups
+    a.grp = rollout ? b->roll_group : 1;
+    const uint64_t K = rollout ? 1u : (uint64_t)b->knob.envs_per_thread;
+    const uint64_t lanes = rollout ? b->B * (uint64_t)a.grp : (b->B + K - 1) / K;
+    const int sb = (replay || rollout) ? BLOCK : b->step_block;
+    const int grid = replay    ? b->grid_for(lanes, b->bpc_base)
+                     : rollout ? b->grid_for(lanes, b->bpc_roll, sb)
+                               : b->grid_for(lanes, b->bpc_step, sb);
+    int e = launch_step(b->W, a, store, replay, sb, grid, b->stream);
+    if (e) return fail(PBN_E_HIP, "k_step launch: %s", hipGetErrorString((hipError_t)e));
+    return timed ? b->ev_end(stop) : 0;
+}
+
+// Step mode is launch-bound between kernels (one HBM pass each): runs of step launches go out
+// as captured HIP graphs -- the same kernels with the same arguments, except that the update
+// counter comes from device memory (*ubase + k for launch k; k_bump adds the graph's length at
+// its end), so one instantiated graph per length serves every replay. Lengths 64, 32, ..., 2 are
+// all captured at the first call of two or more steps; a call of n steps replays 64-graphs, then
+// the binary digits of the rest (n = 20: the 16- and the 4-graph), then one plain launch if n is odd.
+static bool step_graph_ready(pbn_batch* b) {
+    if (b->sg.built) return true;
+    if (b->sg.broken || b->sg.off || !b->stream) return false;  // the null stream cannot capture
+    if (b->sg.ubase.ensure(64)) return false;
+    bool ok = true;
+    for (int j = 0; ok && j < STEP_GRAPH_SIZES; ++j) {
+        const uint32_t K = STEP_GRAPH_K >> j;
+        hipGraph_t g = nullptr;
+        ok = hipStreamBeginCapture(b->stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
+        bool launched = ok;
+        for (uint32_t k = 0; launched && k < K; ++k)
+            launched = step_launch(b, 1, k, 0, nullptr, nullptr, (const uint64_t*)b->sg.ubase.p, false) == 0;
+        if (launched) launched = launch_bump((uint64_t*)b->sg.ubase.p, K, b->stream) == 0;
+        if (ok) ok = hipStreamEndCapture(b->stream, &g) == hipSuccess && launched && g;
+        if (ok) ok = hipGraphInstantiate(&b->sg.graph[j], g, nullptr, nullptr, 0) == hipSuccess;
+        if (g) (void)hipGraphDestroy(g);
+    }
+    if (!ok) {
+        for (hipGraphExec_t& g : b->sg.graph) {
+            if (g) (void)hipGraphExecDestroy(g);
+            g = nullptr;
+        }
+        b->sg.broken = true;
+        (void)hipGetLastError();  // the failed capture is not the caller's error
+        g_err.clear();
+        return false;
+    }
+    b->sg.built = true;
+    return true;
+}
+
+// Captures n step launches as one graph in a free (or the least recently used) exact-length slot.
+// Returns the slot, or -1 (plain launches / power-of-two graphs then).
+static int exact_graph_build(pbn_batch* b, uint32_t n) {
+    if (n < 2 || n > STEP_GRAPH_K || b->sg.broken || b->sg.off || b->sg.exact_broken || !b->stream)
+        return -1;
+    if (b->sg.ubase.ensure(64)) return -1;
+    // capture and instantiate into a fresh exec first: a failed capture leaves the cached graphs
+    // as they were and marks the batch, so later calls do not re-capture n launches to fail again
+    // no k_bump: pbn_step writes the device counter before every replay of an exact graph
+    hipGraph_t g = nullptr;
+    hipGraphExec_t x = nullptr;
+    bool ok = hipStreamBeginCapture(b->stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
+    bool launched = ok;
+    for (uint32_t k = 0; launched && k < n; ++k)
+        launched = step_launch(b, 1, k, 0, nullptr, nullptr, (const uint64_t*)b->sg.ubase.p, false) == 0;
+    if (ok) ok = hipStreamEndCapture(b->stream, &g) == hipSuccess && launched && g;
+    if (ok) ok = hipGraphInstantiate(&x, g, nullptr, nullptr, 0) == hipSuccess;
+    // upload now, so the first replay (e.g. a timed one) does not pay for it
+    if (ok) ok = hipGraphUpload(x, b->stream) == hipSuccess;
+    if (g) (void)hipGraphDestroy(g);
+    if (!ok) {
+        if (x) (void)hipGraphExecDestroy(x);
+        b->sg.exact_broken = true;
+        (void)hipGetLastError();
+        g_err.clear();
+        return -1;
+    }
+    int slot = 0;
+    for (int j = 1; j < pbn_batch::StepGraphs::EXACT_GRAPHS; ++j)
+        if (b->sg.exact_used[j] < b->sg.exact_used[slot]) slot = j;
+    if (b->sg.exact_graph[slot]) {
+        // the evicted exec may still be queued or running from an earlier asynchronous pbn_step on
+        // this stream (HIP documents no deferred free): drain the stream first. Eviction happens
+        // only at capture time, never in a steady replay loop.
+        if (hipStreamSynchronize(b->stream) != hipSuccess) {
+            (void)hipGraphExecDestroy(x);
+            (void)fail(PBN_E_HIP, "stream sync before graph eviction failed");
+            return -1;
+        }
+        (void)hipGraphExecDestroy(b->sg.exact_graph[slot]);
+    }
+    b->sg.exact_graph[slot] = x;
+    b->sg.exact_n[slot] = n;
+    b->sg.exact_used[slot] = ++b->sg.exact_clock;
+    return slot;
+}
+
+static int exact_graph_find(pbn_batch* b, uint32_t n) {
+    for (int j = 0; j < pbn_batch::StepGraphs::EXACT_GRAPHS; ++j)
+        if (b->sg.exact_graph[j] && b->sg.exact_n[j] == n) return j;
+    return -1;
+}
+
+static bool stream_capturing(pbn_batch* b) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (b->stream && hipStreamIsCapturing(b->stream, &cap) != hipSuccess) return true;
+    return cap != hipStreamCaptureStatusNone;
+}
+
+// device counter <- update_count (two 32-bit memsets: stream-ordered, no host buffer)
+static int upload_update_count(pbn_batch* b) {
+    uint32_t* c = (uint32_t*)b->sg.ubase.p;
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)c, (int)(uint32_t)b->update_count, 1, b->stream));
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(c + 1), (int)(uint32_t)(b->update_count >> 32), 1, b->stream));
+    return 0;
+}
+
+// Replay / forced node indices name an updatable node (truth-table networks never update node 0); k53, if given, < 2^53.
+static int check_replay_nodes(const pbn_batch* b, const char* what, const uint32_t* node_idx, const uint64_t* k53,
+                              uint64_t n) {
+    const uint32_t lo = (uint32_t)b->net->kind == PBN_KIND_PROB_TABLE ? 1u : 0u;
+    for (uint64_t q = 0; q < n; q++) {
+        if (node_idx[q] >= (uint32_t)b->N || node_idx[q] < lo)
+            return fail(PBN_E_RANGE, "%s node index %u outside [%u, %d)", what, node_idx[q], lo, b->N);
+        if (k53 && k53[q] >> 53) return fail(PBN_E_RANGE, "replay k53 must be < 2^53");
+    }
+    return 0;
+}
+
+extern "C" {
+
+int pbn_step_prepare(pbn_batch* b, uint32_t n_updates) {
+    CHECK_NN(b, "batch");
+    if (n_updates > PBN_STEP_PREPARE_MAX)
+        return fail(PBN_E_INVALID, "n_updates=%u above PBN_STEP_PREPARE_MAX", n_updates);
+    SET_DEV(b);
+    if (n_updates < 2 || b->sg.off || stream_capturing(b)) return 0;
+    // on failure pbn_step falls back to plain launches; runs longer than STEP_GRAPH_K replay the
+    // power-of-two graphs (one graph of thousands of launches replayed slower: 3.43 vs 3.16 us per
+    // launch at 65,536 Bittner-28 envs)
+    if (n_updates > STEP_GRAPH_K) (void)step_graph_ready(b);
+    else if (exact_graph_find(b, n_updates) < 0) (void)exact_graph_build(b, n_updates);
+    return 0;
+}
+
+int pbn_step(pbn_batch* b, uint32_t n_updates) {
+    CHECK_NN(b, "batch");
+    SET_DEV(b);
+    uint32_t t = 0;
+    // not while the caller is capturing the stream into a graph of its own: plain launches then
+    const bool cap = stream_capturing(b);
+    const uint32_t smallest = STEP_GRAPH_K >> (STEP_GRAPH_SIZES - 1);
+    int exact = -1;
+    if (!cap && b->tm.mode != 1 && n_updates >= 2 && !b->sg.off) {
+        exact = exact_graph_find(b, n_updates);
+        // a length seen twice in a row gets its own graph (an RL loop's fixed step count)
+        if (exact < 0 && n_updates == b->sg.last_n && n_updates <= STEP_GRAPH_K)
+            exact = exact_graph_build(b, n_updates);
+    }
+    b->sg.last_n = n_updates;
+    if (exact >= 0) {
+        if (int rc = upload_update_count(b)) return rc;
+        hipEvent_t stop;
+        if (int rc = b->ev_begin(&stop)) return rc;
+        if (b->tm.mode == 2) b->tm.region_launches += n_updates - 1;  // ev_begin counted one
+        HIP_TRY(hipGraphLaunch(b->sg.exact_graph[exact], b->stream));
+        if (int rc = b->ev_end(stop)) return rc;
+        b->sg.exact_used[exact] = ++b->sg.exact_clock;
+        b->update_count += n_updates;
+        return 0;
+    }
+    if (n_updates >= smallest && b->tm.mode != 1 && !cap && step_graph_ready(b)) {
+        if (int rc = upload_update_count(b)) return rc;
+        for (int j = 0; j < STEP_GRAPH_SIZES; ++j) {
+            const uint32_t K = STEP_GRAPH_K >> j;
+            while (n_updates - t >= K && (j == 0 || n_updates - t < 2 * K)) {
+                hipEvent_t stop;
+                if (int rc = b->ev_begin(&stop)) return rc;
+                if (b->tm.mode == 2) b->tm.region_launches += K - 1;  // ev_begin counted one
+                HIP_TRY(hipGraphLaunch(b->sg.graph[j], b->stream));
+                if (int rc = b->ev_end(stop)) return rc;
+                b->update_count += K;
+                t += K;
+            }
+        }
+    }
+    for (; t < n_updates; t++) {
+        if (int rc = step_launch(b, 1, b->update_count, 0, nullptr, nullptr)) return rc;
+        b->update_count++;
+    }
+    return 0;
+}
+
+int pbn_rollout(pbn_batch* b, uint32_t n_updates) {
+    CHECK_NN(b, "batch");
+    if (!n_updates) return 0;
+    SET_DEV(b);
+    if (int rc = step_launch(b, n_updates, b->update_count, 0, nullptr, nullptr)) return rc;
+    b->update_count += n_updates;
+    return 0;
+}
+
+int pbn_step_replay(pbn_batch* b, const uint32_t* node_idx, const uint64_t* k53, uint32_t n_updates) {
+    CHECK_NN(b, "batch");
+    if (!n_updates) return 0;
+    CHECK_NN(node_idx, "node_idx");
+    CHECK_NN(k53, "k53");
+    const uint64_t n = (uint64_t)n_updates * b->B;
+    if (int rc = check_replay_nodes(b, "replay", node_idx, k53, n)) return rc;
+    SET_DEV(b);
+    if (int rc = b->s_replay_i.ensure(4 * n)) return rc;
+    if (int rc = b->s_replay_k.ensure(8 * n)) return rc;
+    HIP_TRY(hipMemcpyAsync(b->s_replay_i.p, node_idx, 4 * n, hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(b->s_replay_k.p, k53, 8 * n, hipMemcpyHostToDevice, b->stream));
+    if (int rc = step_launch(b, n_updates, 0, 1, b->s_replay_i.p, b->s_replay_k.p)) return rc;
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    return 0;
+}
+
+int pbn_step_forced(pbn_batch* b, const uint32_t* node_idx, uint32_t n_updates) {
+    CHECK_NN(b, "batch");
+    if (!n_updates) return 0;
+    CHECK_NN(node_idx, "node_idx");
+    const uint64_t n = (uint64_t)n_updates * b->B;
+    if (int rc = check_replay_nodes(b, "forced", node_idx, nullptr, n)) return rc;
+    SET_DEV(b);
+    if (int rc = b->s_replay_i.ensure(4 * n)) return rc;
+    HIP_TRY(hipMemcpyAsync(b->s_replay_i.p, node_idx, 4 * n, hipMemcpyHostToDevice, b->stream));
+    // replay-mode kernel with no k53 array: update t takes the choice word of Philox step update
+    // update_count + t (the draw pbn_step would use), so the stream stays in step with pbn_step
+    if (int rc = step_launch(b, n_updates, b->update_count, 1, b->s_replay_i.p, nullptr)) return rc;
+    b->update_count += n_updates;
+    HIP_TRY(hipStreamSynchronize(b->stream));  // the staging buffer is reused by the next call
+    return 0;
+}
+
+static MTArgs mt_args(pbn_batch* b) {
+    MTArgs a{};
+    a.state = b->d_state;
+    a.img = b->d_image;
+    a.L = b->net->L;
+    a.B = b->B;
+    a.n_nodes = b->N;
+    a.mt_py = (uint32_t*)b->mt.py.p;
+    a.mt_np = (uint32_t*)b->mt.np.p;
+    a.pos_py = (uint32_t*)b->mt.pos_py.p;
+    a.pos_np = (uint32_t*)b->mt.pos_np.p;
+    a.lane_walk = b->knob.mt_lane_walk ? 1 : 0;
+    return a;
+}
+
+int pbn_mt_seed(pbn_batch* b, const uint64_t* seeds, int init_state) {
+    CHECK_NN(b, "batch");
+    CHECK_NN(seeds, "seeds");
+    const bool table = b->net->kind == PBN_KIND_PROB_TABLE;
+    if (table)  // np.random.seed(s) accepts 0 <= s < 2^32 only
+        for (uint64_t e = 0; e < b->B; e++)
+            if (seeds[e] >> 32) return fail(PBN_E_RANGE, "Seed must be between 0 and 2**32 - 1 (env %llu)",
+                                            (unsigned long long)e);
+    SET_DEV(b);
+    const size_t row = 4 * ((size_t)MT_ROW * b->B + MT_TAIL_PAD);
+    if (int rc = b->mt.py.ensure(row)) return rc;
+    if (int rc = b->mt.pos_py.ensure(4 * b->B)) return rc;
+    if (table) {
+        if (int rc = b->mt.np.ensure(row)) return rc;
+        if (int rc = b->mt.pos_np.ensure(4 * b->B)) return rc;
+    }
+    if (int rc = b->mt.seeds.ensure(8 * b->B)) return rc;
+    HIP_TRY(hipMemcpyAsync(b->mt.seeds.p, seeds, 8 * b->B, hipMemcpyHostToDevice, b->stream));
+    MTArgs a = mt_args(b);
+    a.seeds = (const uint64_t*)b->mt.seeds.p;
+    if (int rc = timed_launch(b, "k_mt_seed", [&] { return launch_mt_seed(b->W, a, b->grid_all(b->B), b->stream); }))
+        return rc;
+    if (init_state) {  // genRandState / PBN.reset(None): the step kernel's init draws
+        a.init_state = 1;
+        if (int rc = timed_launch(b, "k_mt_step (init)", [&] { return launch_mt_step(b->W, a, b->n_cu, b->stream); }))
+            return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    b->mt.ready = 1;
+    return 0;
+}
+
+int pbn_mt_step(pbn_batch* b, uint32_t n_updates) {
+    CHECK_NN(b, "batch");
+    if (!b->mt.ready) return fail(PBN_E_STATE, "pbn_mt_seed has not been called");
+    if (!n_updates) return 0;
+    SET_DEV(b);
+    MTArgs a = mt_args(b);
+    a.T = n_updates;
+    return timed_launch(b, "k_mt_step", [&] { return launch_mt_step(b->W, a, b->n_cu, b->stream); });
+}
+
+// ------------------------------------------------------------------ synchronous update
+int pbn_synch_step(pbn_batch* b, uint32_t n_steps, const uint32_t* perturb_gap_thr) {
+    CHECK_NN(b, "batch");
+    if (!n_steps) return 0;
+    if (perturb_gap_thr)
+        for (int k = 1; k < b->N; k++)
+            if (perturb_gap_thr[k] > perturb_gap_thr[k - 1])
+                return fail(PBN_E_INVALID, "perturb_gap_thr must be non-increasing");
+    SET_DEV(b);
+    SyncArgs a{};
+    a.state = b->d_state;
+    a.img = b->d_image;
+    a.L = b->net->L;
+    a.B = b->B;
+    a.env_base = b->env_base;
+    a.seed = b->seed;
+    a.step_base = b->aux.sync_steps;
+    a.T = n_steps;
+    if (perturb_gap_thr) {
+        if (int rc = b->aux.sync_tab.ensure(4 * (size_t)b->N)) return rc;
+        HIP_TRY(hipMemcpyAsync(b->aux.sync_tab.p, perturb_gap_thr, 4 * (size_t)b->N, hipMemcpyHostToDevice,
+                               b->stream));
+        a.gap_thr = (const uint32_t*)b->aux.sync_tab.p;
+        a.gap_inv_log2 = gap_inv_log2(perturb_gap_thr, b->N);
+    }
+    a.lds_bytes = sync_layout(b->W, b->net->L.bytes, b->N, &a);
+    if (a.lds_bytes > 160u * 1024u) return fail(PBN_E_UNSUPPORTED, "sync LDS footprint %u B too large", a.lds_bytes);
+    const int grid = b->grid_for(b->B, b->bpc_base);
+    if (int rc = timed_launch(b, "k_sync", [&] { return launch_sync(b->W, a, grid, b->stream); })) return rc;
+    b->aux.sync_steps += n_steps;
+    if (perturb_gap_thr) HIP_TRY(hipStreamSynchronize(b->stream));  // table buffer is reused by later calls
+    return 0;
+}
+
+// ------------------------------------------------------------------ SSD histogram
+int pbn_ssd_run(pbn_batch* b, const int32_t* target_nodes, int n_targets, const uint32_t* flip_gap_thr,
+                uint32_t iters, uint64_t* hist) {
+    CHECK_NN(b, "batch");
+    CHECK_NN(target_nodes, "target_nodes");
+    CHECK_NN(hist, "hist");
+    if (n_targets < 1 || n_targets > 12) return fail(PBN_E_UNSUPPORTED, "n_targets=%d outside [1, 12]", n_targets);
+    for (int j = 0; j < n_targets; j++) {
+        if (target_nodes[j] < 0 || target_nodes[j] >= b->N)
+            return fail(PBN_E_RANGE, "target node %d out of range [0, %d)", target_nodes[j], b->N);
+        for (int q = 0; q < j; q++)
+            if (target_nodes[q] == target_nodes[j]) return fail(PBN_E_INVALID, "duplicate target node %d", target_nodes[j]);
+    }
+    if (flip_gap_thr)
+        for (int k = 1; k < b->N; k++)
+            if (flip_gap_thr[k] > flip_gap_thr[k - 1]) return fail(PBN_E_INVALID, "flip_gap_thr must be non-increasing");
+    SET_DEV(b);
+    const size_t nb = (size_t)1 << n_targets;
+    if (int rc = b->aux.ssd_hist.ensure(8 * nb)) return rc;
+    if (int rc = b->aux.ssd_tab.ensure(4 * (size_t)b->N + 4 * (size_t)n_targets)) return rc;
+    uint32_t* d_gap = (uint32_t*)b->aux.ssd_tab.p;
+    int32_t* d_tgt = (int32_t*)(d_gap + b->N);
+    if (flip_gap_thr) HIP_TRY(hipMemcpyAsync(d_gap, flip_gap_thr, 4 * (size_t)b->N, hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(d_tgt, target_nodes, 4 * (size_t)n_targets, hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipMemsetAsync(b->aux.ssd_hist.p, 0, 8 * nb, b->stream));
+    SSDArgs a{};
+    a.state = b->d_state;
+    a.img = b->d_image;
+    a.L = b->net->L;
+    a.B = b->B;
+    a.env_base = b->env_base;
+    a.seed = b->seed;
+    a.iter_base = b->aux.ssd_iters;
+    a.iters = iters;
+    a.n_targets = n_targets;
+    a.targets = d_tgt;
+    a.gap_thr = flip_gap_thr ? d_gap : nullptr;
+    a.gap_inv_log2 = flip_gap_thr ? gap_inv_log2(flip_gap_thr, b->N) : 0.0f;
+    a.hist = (uint64_t*)b->aux.ssd_hist.p;
+    a.error = b->d_error;
+    HIP_TRY(hipMemsetAsync(b->d_error, 0, 4, b->stream));
+    // one wave per env while the batch is small against the chip (the reference's 300 resets).
+    // Crossovers measured on MI355X (tools/ssd_mode_sweep.py, Bittner-200, p = 0.01, G transitions/s):
+    // 4,096 envs shared 19.4 / wave 16.4 / lane 0.9; 16,384: 18.4 / 19.8 / 3.8; 65,536: - / 20.1 / 14.7;
+    // 262,144: - / 19.8 / 39.4
+    a.wave = b->knob.ssd_wave >= 0 ? b->knob.ssd_wave : (b->B <= (uint64_t)b->n_cu * 256u ? 1 : 0);
+    a.dag = a.wave && !b->knob.ssd_serial && (b->net->kind == PBN_KIND_PREDICTOR_MIX || b->net->kmax <= SSD_DAG_KMAX) ? 1 : 0;
+    // chunk resolution with the workgroup's 4 waves on one env while even that leaves SIMDs free
+    if (a.dag && (b->knob.ssd_shared >= 0 ? b->knob.ssd_shared > 0 : b->B <= (uint64_t)b->n_cu * 8u))
+        a.dag = b->knob.ssd_shared > 1 ? b->knob.ssd_shared : SSD_SHARED_WAVES;
+    a.lds_bytes = ssd_layout(b->W, b->net->L.bytes, b->N, n_targets, &a);
+    if (a.lds_bytes > 160u * 1024u) return fail(PBN_E_UNSUPPORTED, "SSD LDS footprint %u B too large", a.lds_bytes);
+    const uint64_t envs_per_block = a.dag > 1 ? 1u : BLOCK / 64;
+    const int grid = a.wave ? (int)std::min<uint64_t>((b->B + envs_per_block - 1) / envs_per_block, (uint64_t)b->n_cu * 8u)
+                            : b->grid_for(b->B, b->bpc_base);
+    if (int rc = timed_launch(b, "k_ssd", [&] { return launch_ssd(b->W, a, grid, b->stream); })) return rc;
+    std::vector<uint64_t> h(nb);
+    int32_t err = 0;
+    HIP_TRY(hipMemcpyAsync(h.data(), b->aux.ssd_hist.p, 8 * nb, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipMemcpyAsync(&err, b->d_error, 4, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    if (err) return fail(PBN_E_HIP, "k_ssd_wave: a wave timed out waiting for its turn (internal error)");
+    for (size_t k = 0; k < nb; k++) hist[k] += h[k];
+    b->aux.ssd_iters += iters;
+    return 0;
+}
+
+}  // extern "C"

@@ -2,7 +2,7 @@
 //
 // One lane owns one env: its W = ceil(N/64) state words live in VGPRs for the
 // whole launch; the network tables live in LDS (staged once per workgroup from
-// a packed "image" built on the host, see pbn_abi.cpp: build_image()).
+// a packed "image" built on the host, see pbn_image.cpp: build_predictor_image / build_table_image).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -63,23 +63,7 @@ __device__ __forceinline__ void philox_draw_sk(uint64_t seed, uint32_t c0, uint3
     philox4x32_10(w, k0, k1);
 }
 
-// Draws of the step and R6 streams use two 32-bit words per update: the node word and the
-// predictor-choice uniform a, taken as k53 = a << 21 | a >> 11 (32 random bits spread over the
-// 53-bit grid, monotone in a, so the integer thresholds decide the choice exactly; choice
-// probabilities exact to 2^-32). One Philox call (four words) thus serves two updates:
-//   STREAM_STEP: update u of env g takes call {u, g >> 1}, words 2(g & 1) and 2(g & 1) + 1 (envs
-//                2m and 2m + 1 share a call);
-//   STREAM_ENV:  update u of an env step takes call {u >> 1, call index}, words 2(u & 1), +1.
-// Shared with oracle/pbn_oracle.c (u32_k53, step_words).
-__device__ __forceinline__ uint64_t u32_k53(uint32_t a) { return ((uint64_t)a << 21) | (uint64_t)(a >> 11); }
-
-// Threshold T re-expressed on a: the smallest a with u32_k53(a) >= T (2^32 = never), so that
-// u32_k53(a) >= T <=> a >= u32_threshold(T) (u32_k53 is monotone; u32_k53(T >> 21 - 1) < T).
-__device__ __forceinline__ uint64_t u32_threshold(uint64_t T) {
-    const uint64_t a0 = T >> 21;
-    if (a0 >= (1ull << 32)) return 1ull << 32;
-    return u32_k53((uint32_t)a0) >= T ? a0 : a0 + 1u;
-}
+// u32_k53 / u32_threshold (the choice word on the 53-bit grid): pbn_params.hpp, shared with the host.
 
 // Lanes 2k and 2k + 1 swap a word (DPP quad_perm [1,0,3,2]). A lane whose partner is inactive
 // gets its own value back.
@@ -243,32 +227,7 @@ __device__ __forceinline__ uint64_t predictor_record(uint32_t i, uint64_t k53, c
     return reinterpret_cast<const uint64_t*>(tbl + L.off_rec)[i * L.pmax + predictor_choice(i, k53, tbl, L)];
 }
 
-// Compact LDS image of the Philox-driven predictor-mix kernels (k_step, k_rollout), whose choice
-// uniform is a 32-bit word a (k53 = u32_k53(a)): thresholds re-expressed on a (u32_threshold)
-// and stored as u32, rows padded to tp4 (a multiple of 4) so one ds_read_b128 serves 4 of them
-// -- half the LDS bytes of the u64 thresholds, whose random-node reads are the most
-// bank-conflicted reads of an update. u32_threshold can be 2^32 ("never": the u64 padding, or
-// a threshold above k53(2^32 - 1)); it is stored saturated to 2^32 - 1, which a = 2^32 - 1
-// passes. Thresholds are non-decreasing, so the never-entries of a node are its last tp - m_i;
-// record slots q >= m_i all hold record m_i (slot rs >= tp4 + 1 per node), and the count's
-// overshoot at a = 2^32 - 1 lands on the same record. Bit-exact with predictor_record(i, u32_k53(a)).
-// Layout: thr32 [N][tp4] at 0, records u64 [N][rs] at rec_off (16-aligned). For pmax <= 3 it is
-// larger than the u64 image, so the kernels that stage it place their planes at L.plane_off =
-// max(L.bytes, its size); L.bytes itself stays the u64 image's size (what every other kernel and
-// the env config stage). The host builds it (build_predictor_image, pbn_abi.cpp) and appends it
-// to the device image at offset L.bytes.
-struct Thr32 {
-    uint32_t tp4, rs, rec_off, bytes;
-};
-
-__device__ __forceinline__ Thr32 thr32_layout(const NetLayout& L) {
-    Thr32 X;
-    X.tp4 = (L.tp + 3u) & ~3u;
-    X.rs = X.tp4 + 1u > L.pmax ? X.tp4 + 1u : L.pmax;
-    X.rec_off = ((uint32_t)L.n_nodes * X.tp4 * 4u + 15u) & ~15u;
-    X.bytes = (X.rec_off + (uint32_t)L.n_nodes * X.rs * 8u + 15u) & ~15u;
-    return X;
-}
+// Thr32 / thr32_layout (the compact LDS image of the Philox-driven predictor-mix kernels): pbn_params.hpp.
 
 // Record slot of node i's row chosen by the choice word a (compact thresholds at lds[0]).
 __device__ __forceinline__ uint32_t predictor_choice32(uint32_t i, uint32_t a, const uint8_t* lds, uint32_t tp4) {
@@ -321,21 +280,10 @@ __device__ __forceinline__ uint32_t table_eval_lds(const P_t& P, uint32_t i, uin
     return k53 < t ? 1u : 0u;
 }
 
-// Env record (k_env, cooperative-draw mode): predictor record rec (in0 | in1<<16 | in2<<32 | tt<<48)
-// of node i re-encoded for the LDS state planes of k_env's workgroups (ENV_BLOCK lanes): byte offsets of the plane
-// dwords holding in0 / in1 (x), in2 / node i (y), tt | i << 16
-// (w): the bit positions of in0, in1, in2, i in those dwords (one byte each). An update then reads
-// its four plane dwords with no index arithmetic. Inputs are < 512 (W <= 8), so every offset is
-// < 16 KiB.
-// w: the truth table | the LDS byte address of node i's counter deltas (nd_off = the table's offset,
-// 8 B per node; the R6 kernel's LDS stays below 64 KiB) << 16
+// Env record (k_env, cooperative-draw mode) as the uint4 the kernel reads: env_record_words, pbn_params.hpp.
 __device__ __forceinline__ uint4 env_record(uint64_t rec, uint32_t i, uint32_t nd_off) {
-    const uint32_t x0 = (uint32_t)rec & 0xFFFFu, x1 = (uint32_t)(rec >> 16) & 0xFFFFu,
-                   x2 = (uint32_t)(rec >> 32) & 0xFFFFu;
-    auto off = [](uint32_t x) { return (x >> 5) * (uint32_t)(ENV_BLOCK * 4); };
-    return make_uint4(off(x0) | (off(x1) << 16), off(x2) | (off(i) << 16),
-                      (x0 & 31u) | ((x1 & 31u) << 8) | ((x2 & 31u) << 16) | ((i & 31u) << 24),
-                      (uint32_t)(rec >> 48) | ((nd_off + 8u * i) << 16));
+    const EnvRecord r = env_record_words(rec, i, nd_off);
+    return make_uint4(r.x, r.y, r.z, r.w);
 }
 
 // Async update of node i in place on the plane; returns 1 if the bit changed.

@@ -102,7 +102,7 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
     const uint32_t N = (uint32_t)a.L.n_nodes;
     const Thr32 X = thr32_layout(a.L);
     if (GEN && a.gen_img) {
-        // the host-built LDS image (pbn_abi.cpp env_gen_image): the same bytes as the construction below
+        // the host-built LDS image (pbn_image.cpp env_gen_image): the same bytes as the construction below
         stage_image(reinterpret_cast<const uint4*>(a.gen_img), (a.L.bytes + a.erec_shift) / 16, reinterpret_cast<uint4*>(lds));
     } else if constexpr (GEN) {
         // LDS: the thresholds as staged; in place of the 8-B predictor records, 16-B "env

@@ -1,0 +1,372 @@
+// pbn_host.hpp -- internal header of the host side of libpbnsim.so (pbn_abi*.cpp, pbn_image.cpp).
+//
+// The objects behind the C ABI's opaque handles, the error string and the small helpers more than one
+// file uses. pbn_image.cpp (the packers) defines PBN_HOST_NO_HIP before including it: the part above the
+// guard makes no use of HIP, so the packers compile and run with no HIP header (tests/host/image_check.cpp).
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <cstring>
+#include <map>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#ifndef PBN_HOST_NO_HIP
+#include <hip/hip_runtime_api.h>
+#endif
+
+#include "../../include/pbn_abi.h"
+#include "pbn_params.hpp"
+
+using namespace pbn;
+
+// functions and objects shared between the host files are internal: the library exports the C ABI of pbn_abi.h only
+#define PBN_HIDDEN __attribute__((visibility("hidden")))
+
+// The calling thread's last error message (pbn_last_error): one object for every file, defined in pbn_image.cpp.
+extern PBN_HIDDEN thread_local std::string g_err;
+PBN_HIDDEN int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+
+#define CHECK_NN(p, name) \
+    if (!(p)) return fail(PBN_E_INVALID, "%s is NULL", name)
+
+inline uint32_t align16(uint32_t x) { return (x + 15u) & ~15u; }
+
+// One device copy per device of a host blob that never changes once uploaded (the network image, an env
+// config's image, its reset cubes, its cooperative-draw image). Methods: pbn_abi.cpp.
+struct DevCache {
+    std::mutex mu;
+    std::map<int, void*> dev;
+    PBN_HIDDEN const void* on(int device, const void* host, size_t bytes);  // nullptr: the upload failed (nothing is kept)
+    PBN_HIDDEN void release();
+};
+
+struct pbn_net {
+    int kind = 0, N = 0, W = 0;
+    int kmax = 0;                // truth-table networks: most inputs of one node
+    std::vector<uint8_t> image;  // host copy of the LDS image (predictor mix: the compact image follows L.bytes)
+    NetLayout L{};
+    DevCache dev_image;
+    const void* image_on(int device) { return dev_image.on(device, image.data(), image.size()); }
+};
+
+struct pbn_envcfg {
+    const pbn_net* net = nullptr;
+    int W = 0, H = 0, H_reset = 0;
+    std::vector<uint8_t> image;  // net image + cubes [H][2][W] + target [2][W]
+    NetLayout L{};
+    uint32_t off_cubes = 0, off_target = 0, off_ndelta = 0;
+    int fast = 0;
+    std::vector<uint64_t> reset;  // care [H_reset][W], then value [H_reset][W]
+    int32_t horizon = 100, reward_success = 1000, action_cost = 1, first_tested = 0;
+    std::mutex mu;                   // guards gen_image's construction
+    std::vector<uint8_t> gen_image;  // k_env modes 2/4: the LDS image as staged (env_gen_image), built once
+                                     // (erec_shift is fixed by the network and the cubes)
+    DevCache dev_image, dev_reset, dev_gen;
+};
+
+// The packers (pbn_image.cpp): offset arithmetic and memcpy, no device call.
+PBN_HIDDEN int build_predictor_image(const pbn_net_desc* d, pbn_net* n);
+PBN_HIDDEN int build_table_image(const pbn_net_desc* d, pbn_net* n);
+PBN_HIDDEN int build_envcfg_image(const pbn_net& net, const pbn_envcfg_desc* d, pbn_envcfg* c);
+PBN_HIDDEN std::vector<uint8_t> env_gen_image(const pbn_envcfg* cfg, uint32_t erec_shift);
+PBN_HIDDEN uint64_t net_select_u32(const pbn_net* n, int32_t node, uint32_t a);
+
+#ifndef PBN_HOST_NO_HIP
+#define HIP_TRY(expr)                                                                              \
+    do {                                                                                           \
+        hipError_t _e = (expr);                                                                    \
+        if (_e != hipSuccess) return fail(PBN_E_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
+    } while (0)
+#define SET_DEV(b) HIP_TRY(hipSetDevice((b)->device))
+
+struct DevBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    int ensure(size_t bytes) {
+        if (bytes <= cap) return 0;
+        release();
+        hipError_t e = hipMalloc(&p, bytes);
+        if (e != hipSuccess) return fail(PBN_E_NOMEM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
+        cap = bytes;
+        return 0;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+};
+
+// Pinned host staging for small transfers (single envs, small batches): pageable copies of a
+// few bytes cost several microseconds each in the runtime's staging path.
+struct PinBuf {
+    static constexpr size_t CAP = 64 * 1024;
+    uint8_t* p = nullptr;
+    bool ready() {
+        if (!p && hipHostMalloc((void**)&p, CAP, hipHostMallocDefault) != hipSuccess) p = nullptr;
+        return p != nullptr;
+    }
+    void release() {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+    }
+};
+
+// The device-open prologue of pbn_batch_create and pbn_reach_create.
+inline int open_device(int device) {
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev < 1)
+        return fail(PBN_E_HIP, "no HIP device available (hipGetDeviceCount: %s); libpbnsim has no CPU path",
+                    hipGetErrorString(e));
+    if (device < 0 || device >= ndev) return fail(PBN_E_RANGE, "device %d outside [0, %d)", device, ndev);
+    HIP_TRY(hipSetDevice(device));
+    return 0;
+}
+
+inline int check_action_shape(int A, int offset) {
+    if (A < 1 || A > 4096) return fail(PBN_E_INVALID, "A=%d outside [1, 4096]", A);
+    if (offset != 0 && offset != 1) return fail(PBN_E_INVALID, "offset must be 0 or 1");
+    return 0;
+}
+
+constexpr uint32_t STEP_GRAPH_K = 64;  // longest captured run of step launches
+constexpr int STEP_GRAPH_SIZES = 6;     // graphs of 64, 32, 16, 8, 4 and 2 launches
+constexpr uint64_t STEP_GRAPH_MAX_WORDS = 1ull << 20;  // state words from which step mode launches plainly
+
+// Launch knobs read from PBNSIM_* once at pbn_batch_create (read_knobs, pbn_abi.cpp): measurement / tests.
+struct Knobs {
+    int store_mode = STORE_DIRTY;  // PBNSIM_STORE_MODE
+    int envs_per_thread = 2;       // PBNSIM_ENVS_PER_THREAD: K, envs each thread walks per launch (pipelined)
+    int step_block = 0;            // PBNSIM_STEP_BLOCK: 256 / 1024 threads per workgroup of the step kernel, 0 = by size
+    int step_graph = -1;           // PBNSIM_STEP_GRAPH=0/1 forces step mode without / with HIP graphs, -1 = by size
+    int roll_group = -1;           // PBNSIM_ROLL_GROUP: lanes per env of the rollout kernel, -1 = by size
+    bool env_no_gen = false;  // PBNSIM_ENV_NO_GEN: no cooperative draw generation
+    int env_group = 0;        // PBNSIM_ENV_GROUP: lanes per env (1 = lane mode), 0 = by batch size
+    int env_bpc = 0;          // PBNSIM_ENV_BPC: cap on resident workgroups per CU, 0 = none
+    int env_chunk = 0;        // PBNSIM_ENV_CHUNK: draw-round chunk 32 / 48 of the cooperative-draw kernels, 0 = auto
+    int env_grid_cap = 0;     // PBNSIM_ENV_GRID: the R6 kernel's workgroups (tests: lane refill, hand-offs), 0 = by size
+    int env_tail = -1;        // PBNSIM_ENV_TAIL: the R6 kernel's tail-mode threshold (live envs per wave), -1 = default
+    int env_lane_limit = 0;   // PBNSIM_ENV_LANES: lanes per wave taking envs in the tail-mode kernel, 0 = auto
+    bool env_steal = true;    // PBNSIM_ENV_STEAL=0: no hand-off of tail envs between a workgroup's waves (k_env, mode 4)
+    bool env_kernel_image = false;  // PBNSIM_ENV_KERNEL_IMAGE=1: k_env builds its LDS image (no host-built image)
+    int env_helpers = 3;      // PBNSIM_ENV_HELPERS: at most this many tail helpers per session (0-3; 0 = off)
+    // PBNSIM_ENV_GRID_STEAL: grid-wide hand-off of tail envs (k_env, mode 4): 1 on, 0 off, unset = fused launches
+    // and update caps from GPOOL_MIN_CAP (below it one env step's loops are too short to repay the waiting
+    // workgroups' residency)
+    int env_grid_steal = -1;
+    int env_pool_cu_idle = -1;    // PBNSIM_ENV_POOL_CU_IDLE: 1 only idle CUs take pool tickets, 0 any idle workgroup,
+                                  // -1 = the default (1)
+    int env_grid_slots = 0;      // PBNSIM_ENV_GRID_SLOTS: pool slots in use (measurement: 1 keeps the waiting workgroups
+                                 // resident but moves at most one env), 0 = GPOOL_CAP
+    int ssd_wave = -1;        // PBNSIM_SSD_WAVE: 1 = one wave per env, 0 = one lane per env, -1 = by size
+    bool ssd_serial = false;  // PBNSIM_SSD_SERIAL=1: wave mode applies each chunk serially (no chunk DAG)
+    int ssd_shared = -1;      // PBNSIM_SSD_SHARED: 0 = one wave per env, 4 / 8 = that many, 1 = the default
+                              // count, -1 = by size
+    bool mt_lane_walk = false;  // PBNSIM_MT_LANES=1: MT-mode steps of predictor-mix networks on k_mt_step
+};
+
+// What env_plan (pbn_abi_env.cpp) decides for one R6 launch; the batch keeps the last launched one.
+struct EnvPlan {
+    int mode = -1;            // EnvArgs::fast: 0 cube matching, 1 byte counters, 2 cooperative draws, 3 group mode, 4 tail kernel
+    int grp = 0;              // lanes per env
+    uint32_t erec_shift = 0;  // LDS bytes the 16-B env records add (modes 2 / 4)
+    uint32_t chunk = 0;       // draw-round chunk (modes 2 / 4)
+    int bpc = 1;              // resident workgroups per CU
+    uint32_t lane_limit = 0, tail_max = 0;
+    int grid = 0;             // workgroups
+    bool host_image = false;  // the kernel stages the host-built image (env_gen_image)
+    bool handoff = false;     // tail hand-off between a workgroup's waves
+    bool gpool = false;       // grid-wide hand-off (grid pool)
+    int kernel = -1;          // pbn_batch_info.env_kernel
+    int error = 0;            // hipError_t of a failed occupancy query: no launch
+};
+
+struct pbn_batch {
+    pbn_net* net = nullptr;
+    int device = 0, W = 0, N = 0;
+    hipStream_t stream = nullptr;      // the stream every call of this batch runs on
+    hipStream_t own_stream = nullptr;  // created with the batch; `stream` unless pbn_batch_set_stream
+    uint64_t B = 0, env_base = 0, seed = 0, update_count = 0;
+    uint32_t reset_count = 0;
+    uint64_t* d_state = nullptr;
+    int64_t* d_nsteps = nullptr;
+    int32_t* d_error = nullptr;
+    const void* d_image = nullptr;
+    int n_cu = 0, bpc_step = 1, bpc_base = 1, bpc_roll = 1;
+    int step_block = 1024;  // threads per workgroup of the Philox step kernel (256 or 1024)
+    int roll_group = 1;     // lanes per env of the rollout kernel
+    Knobs knob;
+    PinBuf pin;                         // staging for small host<->device copies
+    DevBuf s_flip_err;                  // range-error flag of pbn_flip_device
+    DevBuf s_act, s_obs, s_rew, s_flags, s_nup, s_replay_i, s_replay_k, s_off, s_mask;
+
+    struct StepGraphs {
+        // step mode without HIP graphs: by default for large batches (a graph replay's start on the
+        // device costs more than host submission, which a long kernel hides: 1M Bittner-200 envs, 20
+        // launches: 9.3 us per launch plain vs 9.9 us as one replay); PBNSIM_STEP_GRAPH=0/1 forces it
+        bool off = false;
+        // graph[j]: (STEP_GRAPH_K >> j) step launches + k_bump, captured once (all sizes at the
+        // first call of two or more steps)
+        hipGraphExec_t graph[STEP_GRAPH_SIZES] = {};
+        bool built = false;
+        bool broken = false;        // capture or instantiation failed once: plain launches
+        bool exact_broken = false;  // an exact-length capture failed once: no more of them
+        // exact-length graphs: one replay for a whole call of n steps (pbn_step_prepare, or the second
+        // call with the same n); each extra replay in a call costs a graph start on the device (~13 us)
+        static constexpr int EXACT_GRAPHS = 4;
+        uint32_t exact_n[EXACT_GRAPHS] = {};
+        hipGraphExec_t exact_graph[EXACT_GRAPHS] = {};
+        uint64_t exact_used[EXACT_GRAPHS] = {};  // LRU stamps
+        uint64_t exact_clock = 0;
+        uint32_t last_n = 0;
+        DevBuf ubase;  // device copy of update_count for graph replays
+    } sg;
+    struct R6 {
+        uint32_t calls = 0;        // env steps launched (Philox call index)
+        DevBuf counter;            // env-step work-queue head
+        DevBuf steal;              // k_env tail hand-off: count of envs handed off
+        DevBuf gpool;              // k_env grid pool: control words, slot states, slots
+        uint32_t gpool_epoch = 0;  // the last R6 launch's pool epoch
+        bool fault_check = false;  // a device-path env launch used the grid pool since the last pbn_sync
+        EnvPlan last;              // of the last R6 launch
+    } r6;
+    struct MT {
+        DevBuf py, np, pos_py, pos_np, seeds;  // allocated by pbn_mt_seed
+        int ready = 0;
+    } mt;
+    struct Aux {
+        DevBuf ssd_hist, ssd_tab;  // SSD histogram + gap/target tables
+        uint64_t ssd_iters = 0;    // SSD iteration counter (Philox)
+        DevBuf sync_tab;           // perturbation gap table
+        uint64_t sync_steps = 0;   // synchronous-step counter (Philox)
+    } aux;
+    // timing: mode 1 = an event pair around every launch; mode 2 = one region
+    // (start before the first launch after enabling, stop after the latest launch)
+    struct Timing {
+        int mode = 0;
+        std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
+        size_t ev_used = 0;
+        uint64_t region_launches = 0;
+        bool region_closed = false;
+        hipEvent_t region_start = nullptr;  // ev_pool[0].first once the region's first launch is queued
+        hipEvent_t region_end = nullptr;    // the closed region's stop event
+    } tm;
+
+    int grid_for(uint64_t items, int bpc, int block = BLOCK) const {
+        uint64_t need = (items + block - 1) / block;
+        uint64_t cap = (uint64_t)n_cu * (uint64_t)bpc;
+        uint64_t g = std::min<uint64_t>(need, cap);
+        return (int)std::max<uint64_t>(g, 1);
+    }
+    int grid_all(uint64_t items) const { return (int)std::max<uint64_t>((items + BLOCK - 1) / BLOCK, 1); }
+    int ev_new_pair() {
+        hipEvent_t a, b;
+        HIP_TRY(hipEventCreate(&a));
+        HIP_TRY(hipEventCreate(&b));
+        tm.ev_pool.emplace_back(a, b);
+        return 0;
+    }
+    int ev_begin(hipEvent_t* stop) {
+        *stop = nullptr;
+        if (!tm.mode) return 0;
+        if (tm.mode == 2) {
+            if (tm.ev_pool.empty())
+                if (int rc = ev_new_pair()) return rc;
+            if (tm.region_launches == 0) {
+                HIP_TRY(hipEventRecord(tm.ev_pool[0].first, stream));
+                tm.region_start = tm.ev_pool[0].first;
+            }
+            tm.region_launches++;
+            tm.ev_used = 1;
+            return 0;  // the stop event is recorded once: pbn_timing_enable(0) or pbn_timing_read
+        }
+        if (tm.ev_used == tm.ev_pool.size())
+            if (int rc = ev_new_pair()) return rc;
+        auto& pr = tm.ev_pool[tm.ev_used++];
+        HIP_TRY(hipEventRecord(pr.first, stream));
+        *stop = pr.second;
+        return 0;
+    }
+    int ev_end(hipEvent_t stop) {
+        if (stop) HIP_TRY(hipEventRecord(stop, stream));
+        return 0;
+    }
+};
+
+// ev_begin; launch; ev_end around one kernel launch (`launch` returns the launcher's hipError_t as int).
+template <class F>
+inline int timed_launch(pbn_batch* b, const char* kernel, F&& launch) {
+    hipEvent_t stop;
+    if (int rc = b->ev_begin(&stop)) return rc;
+    if (int e = launch()) return fail(PBN_E_HIP, "%s launch: %s", kernel, hipGetErrorString((hipError_t)e));
+    return b->ev_end(stop);
+}
+
+// pbn_abi.cpp; used by the R6 entry points too
+PBN_HIDDEN int validate_actions(const pbn_batch* b, const int32_t* actions, int A, int offset);
+PBN_HIDDEN int h2d(pbn_batch* b, void* dst, const void* src, size_t bytes);
+PBN_HIDDEN int run_init(pbn_batch* b, const pbn_envcfg* cfg, const void* d_mask, const void* care, const void* value);
+
+// Attractor discovery (pbn_reach.hip); entry points in pbn_abi_reach.cpp.
+struct pbn_reach {
+    pbn_net* net = nullptr;
+    int device = 0, W = 0;
+    hipStream_t stream = nullptr;
+    const void* d_image = nullptr;
+    uint32_t max_states = 0, key_cap = 0, tcap = 0, fcap = 0;
+    DevBuf keys, mark, table, ctl, queue, free_ring, hull, in, out;
+    uint32_t* h_ctl = nullptr;  // pinned [REACH_CTL_WORDS + 1]: the control words, one word to send
+    uint32_t free_limit = 0;    // free-ring positions below this are safe to take in the running level
+    bool free_any = false;
+    uint32_t n_keys = 0;        // entries reserved (live and dead) by the last closure
+    uint32_t count = 0;         // live entries
+    uint32_t epoch = 0;         // of the last mark_backward (0: none since the closure)
+    bool complete = false;
+
+    ReachArgs args() const {
+        ReachArgs a{};
+        a.img = d_image;
+        a.L = net->L;
+        a.keys = (uint64_t*)keys.p;
+        a.mark = (uint32_t*)mark.p;
+        a.table = (unsigned long long*)table.p;
+        a.ctl = (uint32_t*)ctl.p;
+        a.queue = (uint32_t*)queue.p;
+        a.free_ring = (uint32_t*)free_ring.p;
+        a.fmask = fcap - 1u;
+        a.free_limit = free_limit;
+        a.free_any = free_any ? 1u : 0u;
+        a.hull = (unsigned long long*)hull.p;
+        a.tmask = tcap - 1u;
+        a.key_cap = key_cap;
+        a.max_states = max_states;
+        a.epoch = epoch;
+        return a;
+    }
+    int read_ctl() {
+        HIP_TRY(hipMemcpyAsync(h_ctl, ctl.p, 4 * REACH_CTL_WORDS, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        return 0;
+    }
+    // one wave per frontier entry, at most REACH_CHUNK entries and REACH_MAX_GRID workgroups per launch
+    int sweep(int which, uint32_t lo, uint32_t hi) {
+        for (uint32_t c = lo; c < hi; c += REACH_CHUNK) {
+            ReachArgs a = args();
+            a.lo = c;
+            a.hi = std::min(hi, c + REACH_CHUNK);
+            const uint32_t grid = std::min(REACH_MAX_GRID, (a.hi - a.lo + 3u) / 4u);
+            if (int e = launch_reach(W, which, a, (int)grid, stream))
+                return fail(PBN_E_HIP, "reach launch: %s", hipGetErrorString((hipError_t)e));
+        }
+        return 0;
+    }
+    int upload(const uint64_t* words, uint64_t n) {
+        if (int rc = in.ensure(8 * (size_t)W * n)) return rc;
+        HIP_TRY(hipMemcpyAsync(in.p, words, 8 * (size_t)W * n, hipMemcpyHostToDevice, stream));
+        return 0;
+    }
+};
+#endif  // PBN_HOST_NO_HIP

@@ -53,6 +53,51 @@ struct NetLayout {
     uint32_t plane_off;
 };
 
+// Draws of the step and R6 streams use two 32-bit words per update: the node word and the
+// predictor-choice uniform a, taken as k53 = a << 21 | a >> 11 (32 random bits spread over the
+// 53-bit grid, monotone in a, so the integer thresholds decide the choice exactly; choice
+// probabilities exact to 2^-32). One Philox call (four words) thus serves two updates:
+//   STREAM_STEP: update u of env g takes call {u, g >> 1}, words 2(g & 1) and 2(g & 1) + 1 (envs
+//                2m and 2m + 1 share a call);
+//   STREAM_ENV:  update u of an env step takes call {u >> 1, call index}, words 2(u & 1), +1.
+// Shared with oracle/pbn_oracle.c (u32_k53, step_words), which keeps its own copy.
+constexpr uint64_t u32_k53(uint32_t a) { return ((uint64_t)a << 21) | (uint64_t)(a >> 11); }
+
+// Threshold T re-expressed on a: the smallest a with u32_k53(a) >= T (2^32 = never), so that
+// u32_k53(a) >= T <=> a >= u32_threshold(T) (u32_k53 is monotone; u32_k53(T >> 21 - 1) < T).
+constexpr uint64_t u32_threshold(uint64_t T) {
+    const uint64_t a0 = T >> 21;
+    if (a0 >= (1ull << 32)) return 1ull << 32;
+    return u32_k53((uint32_t)a0) >= T ? a0 : a0 + 1u;
+}
+
+// Compact LDS image of the Philox-driven predictor-mix kernels (k_step, k_rollout), whose choice
+// uniform is a 32-bit word a (k53 = u32_k53(a)): thresholds re-expressed on a (u32_threshold)
+// and stored as u32, rows padded to tp4 (a multiple of 4) so one ds_read_b128 serves 4 of them
+// -- half the LDS bytes of the u64 thresholds, whose random-node reads are the most
+// bank-conflicted reads of an update. u32_threshold can be 2^32 ("never": the u64 padding, or
+// a threshold above k53(2^32 - 1)); it is stored saturated to 2^32 - 1, which a = 2^32 - 1
+// passes. Thresholds are non-decreasing, so the never-entries of a node are its last tp - m_i;
+// record slots q >= m_i all hold record m_i (slot rs >= tp4 + 1 per node), and the count's
+// overshoot at a = 2^32 - 1 lands on the same record. Bit-exact with predictor_record(i, u32_k53(a)).
+// Layout: thr32 [N][tp4] at 0, records u64 [N][rs] at rec_off (16-aligned). For pmax <= 3 it is
+// larger than the u64 image, so the kernels that stage it place their planes at L.plane_off =
+// max(L.bytes, its size); L.bytes itself stays the u64 image's size (what every other kernel and
+// the env config stage). The host builds it (build_predictor_image, pbn_image.cpp) and appends it
+// to the device image at offset L.bytes. This is the one definition, for host and kernels.
+struct Thr32 {
+    uint32_t tp4, rs, rec_off, bytes;
+};
+
+constexpr Thr32 thr32_layout(const NetLayout& L) {
+    Thr32 X{};
+    X.tp4 = (L.tp + 3u) & ~3u;
+    X.rs = X.tp4 + 1u > L.pmax ? X.tp4 + 1u : L.pmax;
+    X.rec_off = ((uint32_t)L.n_nodes * X.tp4 * 4u + 15u) & ~15u;
+    X.bytes = (X.rec_off + (uint32_t)L.n_nodes * X.rs * 8u + 15u) & ~15u;
+    return X;
+}
+
 struct StepArgs {
     uint64_t* state;             // [B][W]
     const void* img;             // network image (device, 16-B aligned)
@@ -129,7 +174,7 @@ struct EnvArgs {
                               // <= tail_max: every wave in tail mode from its first env)
     int32_t steal_local;      // fast == 4: hand-off of tail envs between the waves of a workgroup (LDS)
     uint32_t* steal_count;    // envs handed off in this launch (diagnostics), zeroed per launch
-    const void* gen_img;      // fast == 2 / 4: the LDS image as staged (host-built, pbn_abi.cpp env_gen_image);
+    const void* gen_img;      // fast == 2 / 4: the LDS image as staged (host-built, pbn_image.cpp env_gen_image);
                               // null: the kernel builds it from img
     uint32_t chunk;           // fast == 2 / 4: updates per lane between draw rounds (ENV_CHUNK_SMALL / _LARGE)
     int32_t tail_helpers;     // fast == 4 (with steal_local): up to this many (<= 3) idle waves of the workgroup prepare a long tail
@@ -149,13 +194,35 @@ struct EnvArgs {
                               // 0: as soon as its own waves have run out of work
 };
 
+// Env record (k_env, cooperative-draw mode): predictor record rec (in0 | in1<<16 | in2<<32 | tt<<48)
+// of node i re-encoded for the LDS state planes of k_env's workgroups (ENV_BLOCK lanes): byte offsets of the plane
+// dwords holding in0 / in1 (x), in2 / node i (y), tt | i << 16
+// (w): the bit positions of in0, in1, in2, i in those dwords (one byte each). An update then reads
+// its four plane dwords with no index arithmetic. Inputs are < 512 (W <= 8), so every offset is
+// < 16 KiB.
+// w: the truth table | the LDS byte address of node i's counter deltas (nd_off = the table's offset,
+// 8 B per node; the R6 kernel's LDS stays below 64 KiB) << 16
+struct EnvRecord {
+    uint32_t x, y, z, w;
+};
+
+constexpr uint32_t env_plane_off(uint32_t x) { return (x >> 5) * (uint32_t)(ENV_BLOCK * 4); }
+
+constexpr EnvRecord env_record_words(uint64_t rec, uint32_t i, uint32_t nd_off) {
+    const uint32_t x0 = (uint32_t)rec & 0xFFFFu, x1 = (uint32_t)(rec >> 16) & 0xFFFFu,
+                   x2 = (uint32_t)(rec >> 32) & 0xFFFFu;
+    return EnvRecord{env_plane_off(x0) | (env_plane_off(x1) << 16), env_plane_off(x2) | (env_plane_off(i) << 16),
+                     (x0 & 31u) | ((x1 & 31u) << 8) | ((x2 & 31u) << 16) | ((i & 31u) << 24),
+                     (uint32_t)(rec >> 48) | ((nd_off + 8u * i) << 16)};
+}
+
 constexpr uint32_t GPOOL_GRANULES = 64;  // per slot: the hand-off box as u32 words (10 + 4W <= 64 for W <= 13)
 constexpr uint32_t GPOOL_CAP = 8192;     // grid pool slots (4 MiB); envs past them stay with their wave
 // control words: [0, 16) counters, [GPOOL_CU_WORD + __smid()] workgroups on that CU still on their own envs
 // (__smid() < 1024: XCC, SE, CU id bits); the block is zeroed per launch
 constexpr uint32_t GPOOL_CU_WORD = 16, GPOOL_CTL_BYTES = 4u * (GPOOL_CU_WORD + 1024u);
 // the pool is on by default for fused launches (several env steps) and for launches whose update cap is at least
-// this (pbn_abi.cpp env_launch): one env step at config 5's 4,096 cap lost more to the waiting workgroups'
+// this (pbn_abi_env.cpp env_plan): one env step at config 5's 4,096 cap lost more to the waiting workgroups'
 // residency than the moved envs gave back (1.14 -> 1.18-1.20 ms per step)
 constexpr uint32_t GPOOL_MIN_CAP = 16384;
 

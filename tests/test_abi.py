@@ -93,6 +93,33 @@ def test_batch_create_validates_sizes_on_host():
     assert _lib.lib.pbn_batch_create(None, 0, 16, 0, 1, C.byref(h)) == _lib.PBN_E_INVALID
 
 
+def test_every_host_file_reports_through_one_error_string():
+    """One error path per host translation unit, each reachable without a GPU, sets the message
+    pbn_last_error returns (core: the n_envs check above; packers: the NULL array check above)."""
+    import ctypes as C
+
+    from gym_pbn_amd import _lib
+    from gym_pbn_amd.batch import Net
+    from gym_pbn_amd.network import load_network
+
+    h = C.c_void_p()
+    # pbn_abi_sim.cpp
+    assert _lib.lib.pbn_step(None, 1) == _lib.PBN_E_INVALID
+    assert _lib.last_error() == "batch is NULL"
+    # R6: the env config's descriptor check, and an entry point of pbn_abi_env.cpp
+    net = Net(load_network("bittner28"))
+    d = _lib.EnvCfgDesc()
+    d.n_cubes = -1
+    assert _lib.lib.pbn_envcfg_create(net.handle, C.byref(d), C.byref(h)) == _lib.PBN_E_INVALID
+    assert "n_cubes" in _lib.last_error()
+    assert _lib.lib.pbn_env_reset_device(None, None, None) == _lib.PBN_E_INVALID
+    assert _lib.last_error() == "batch is NULL"
+    # pbn_abi_reach.cpp
+    table = Net(load_network("tt8"))
+    assert _lib.lib.pbn_reach_create(table.handle, 0, 1024, C.byref(h)) == _lib.PBN_E_UNSUPPORTED
+    assert "attractor discovery covers predictor-mix networks" in _lib.last_error()
+
+
 def _u32_threshold(T):
     a0 = T >> 21
     if a0 >= 1 << 32:

@@ -260,7 +260,7 @@ def test_config2_exact_size_matches_oracle(G, oracle_mod):
 def test_exact_graph_eviction_without_host_sync(G, oracle_mod):
     """Six lengths cycled through the four exact-length slots with no host sync between calls: every
     capture past the fourth evicts a graph whose replay may still be queued on the batch stream
-    (pbn_abi.cpp exact_graph_build drains the stream before destroying it). The state after the
+    (pbn_abi_sim.cpp exact_graph_build drains the stream before destroying it). The state after the
     whole run equals the oracle's."""
     net = load_network("bittner199")
     o = oracle_mod.Oracle(net)

@@ -59,7 +59,7 @@ def test_lane_refill_matches_oracle(G, oracle_mod, monkeypatch, mode):
     """... and with either draw-round chunk (EnvArgs::chunk: 48 for these launches, 32 forced by
     PBNSIM_ENV_CHUNK -- the chunk the host picks for long fused launches over large batches); and with
     the kernel building its LDS image itself (PBNSIM_ENV_KERNEL_IMAGE=1) instead of staging the
-    host-built one (pbn_abi.cpp env_gen_image), so both constructions stay exact; and with the workgroups per CU
+    host-built one (pbn_image.cpp env_gen_image), so both constructions stay exact; and with the workgroups per CU
     capped at one (PBNSIM_ENV_BPC=1)."""
     import torch
 

@@ -24,7 +24,9 @@ done
 cd $out/src
 F="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -mcode-object-version=5 -Wno-pass-failed -I$out/include ${flags[*]}"
 for f in csrc/*.hip; do /opt/rocm/bin/hipcc $F -c -o $out/$(basename $f .hip).o $f & done
-g++ -O2 -fPIC -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -I$out/include ${flags[*]} -c -o $out/pbn_abi.o csrc/pbn_abi.cpp
+for f in csrc/*.cpp; do
+  g++ -O2 -fPIC -std=c++17 -fvisibility-inlines-hidden -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -I$out/include ${flags[*]} -c -o $out/$(basename $f .cpp).o $f || exit 1
+done
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $out/libpbnsim.so $out/*.o -L/opt/rocm/lib -lamdhip64
 echo built $out/libpbnsim.so
