@@ -323,7 +323,7 @@ int pbn_batch_get_info(const pbn_batch* b, pbn_batch_info* info) {
     info->env_kernel = p.kernel;
     info->env_lane_limit = (int)p.lane_limit;
     info->env_handoff = p.handoff ? 1 : 0;
-    info->env_chunk = (p.mode == 2 || p.mode == 4) ? (int)p.chunk : 0;
+    info->env_chunk = (p.mode == ENV_MODE_COOP || p.mode == ENV_MODE_TAIL) ? (int)p.chunk : 0;
     return 0;
 }
 

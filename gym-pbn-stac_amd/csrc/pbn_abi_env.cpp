@@ -22,7 +22,7 @@ static int env_reset(pbn_batch* b, const pbn_envcfg* cfg_c, const void* d_mask) 
 // Per-step call, Bittner-200, 1 MI355X (256 CUs): G = 8 beats lane mode up to 32k envs (0.21 vs
 // 0.33 ms at B = 1, 0.88 vs 1.99 ms at 8k, 1.85 vs 2.04 ms at 32k) and loses from 64k on (2.31 vs
 // 2.07 ms; 131k: 3.28 vs 2.60 ms) -- the crossover sits near 48k envs.
-// Group mode (G = 8 lanes per env) for small batches -- except where the tail kernel (k_env mode 4:
+// Group mode (G = 8 lanes per env) for small batches -- except where the tail kernel (k_env ENV_MODE_TAIL:
 // <= 4 cubes and its 16-B env records fit) applies: its tail mode with one env per wave
 // (env_lane_limit) is faster at every batch size measured (profiles/r03_r6_lanes_sweep.json)
 static int env_group_size(const pbn_batch* b, bool tail_kernel) {
@@ -38,37 +38,38 @@ static EnvPlan env_plan(const pbn_batch* b, const pbn_envcfg* cfg, int replay, u
     // cooperative draw generation: predictor mix, Philox, record index fits the u16 entry
     int mode = (cfg->fast && !replay && b->net->kind == KIND_PREDICTOR_MIX && cfg->L.pmax <= 16 &&
                 b->net->N <= 512 && !k.env_no_gen)
-                   ? 2
+                   ? (int)ENV_MODE_COOP
                    : cfg->fast;
     // cooperative-draw mode keeps 16-B env records in LDS where the 8-B predictor records were
     // (env_record_words, pbn_params.hpp): the tables after them move up by erec_shift. Whether they fit is
-    // decided first, so that the group-size rule below knows whether the tail kernel (mode 4) applies
+    // decided first, so that the group-size rule below knows whether the tail kernel (ENV_MODE_TAIL) applies
     uint32_t erec_shift = 0;
     bool erec_fits = false;
-    if (mode == 2) {
+    if (mode == ENV_MODE_COOP) {
         // rows of rs records (thr32_layout: tp4 + 1 slots at least, for the saturated choice)
         const uint32_t nrec = (uint32_t)b->net->N * thr32_layout(cfg->L).rs;
         erec_shift = cfg->L.off_rec + 16u * nrec - cfg->off_cubes;
         erec_fits = nrec <= 65535u &&
-                    env_lds_bytes(b->W, cfg->L.bytes + erec_shift, 2, 1, 0, ENV_CHUNK_SMALL) <= ENV_LDS_MAX;
+                    env_lds_bytes(b->W, cfg->L.bytes + erec_shift, ENV_MODE_COOP, 1, ENV_CHUNK_SMALL) <= ENV_LDS_MAX;
     }
     // group mode (k_env_grp: G lanes per env, G updates per round trip; its rows need no env records)
     int grp = 1;
-    if (mode == 2 && b->net->N <= 256) {
+    if (mode == ENV_MODE_COOP && b->net->N <= 256) {
         grp = k.env_group ? k.env_group : env_group_size(b, erec_fits && cfg->H <= 4);
         if (grp != 2 && grp != 4 && grp != 8) grp = 1;
-        if (grp > 1) mode = 3;
+        if (grp > 1) mode = ENV_MODE_GROUP;
     }
-    if (mode == 2) {
+    if (mode == ENV_MODE_COOP) {
         if (!erec_fits)
             mode = cfg->fast;  // too large for the u16 record index / one workgroup's LDS
         else if (cfg->H <= 4)
-            mode = 4;  // the same kernel with one packed counter word (<= 4 cubes)
-        // mode 4 adds the workgroup hand-off control words: re-check the fit with the final mode
-        if (mode == 4 && env_lds_bytes(b->W, cfg->L.bytes + erec_shift, 4, 1, 0, ENV_CHUNK_SMALL) > ENV_LDS_MAX)
+            mode = ENV_MODE_TAIL;  // the same kernel with one packed counter word (<= 4 cubes)
+        // ENV_MODE_TAIL adds the workgroup hand-off control words: re-check the fit with the final mode
+        if (mode == ENV_MODE_TAIL &&
+            env_lds_bytes(b->W, cfg->L.bytes + erec_shift, ENV_MODE_TAIL, 1, ENV_CHUNK_SMALL) > ENV_LDS_MAX)
             mode = cfg->fast;
     }
-    const bool coop = mode == 2 || mode == 4;
+    const bool coop = mode == ENV_MODE_COOP || mode == ENV_MODE_TAIL;
     if (!coop) erec_shift = 0;
     const uint32_t img = cfg->L.bytes + erec_shift;
     // PBNSIM_ENV_KERNEL_IMAGE=1: the kernel builds its LDS image itself (tests keep that path covered)
@@ -81,10 +82,10 @@ static EnvPlan env_plan(const pbn_batch* b, const pbn_envcfg* cfg, int replay, u
         // (>= 16 env steps per env over a queue of >= 4 envs per lane of the large one's grid), or the large
         // one does not fit one workgroup's 64 KiB; PBNSIM_ENV_CHUNK=32 / 48 overrides
         int bpc_s = 1, bpc_l = 1;
-        p.error = max_blocks_env(b->W, b->net->kind, mode, grp, img, &bpc_s, b->net->N, ENV_CHUNK_SMALL);
-        const bool large_fits = env_lds_bytes(b->W, img, mode, 1, 0, ENV_CHUNK_LARGE) <= ENV_LDS_MAX;
+        p.error = max_blocks_env(b->W, b->net->kind, mode, grp, img, &bpc_s, ENV_CHUNK_SMALL);
+        const bool large_fits = env_lds_bytes(b->W, img, mode, 1, ENV_CHUNK_LARGE) <= ENV_LDS_MAX;
         if (large_fits && !p.error)
-            p.error = max_blocks_env(b->W, b->net->kind, mode, grp, img, &bpc_l, b->net->N, ENV_CHUNK_LARGE);
+            p.error = max_blocks_env(b->W, b->net->kind, mode, grp, img, &bpc_l, ENV_CHUNK_LARGE);
         const uint64_t lanes_l = (uint64_t)b->n_cu * (uint64_t)bpc_l * ENV_BLOCK;
         const bool throughput = n_calls >= 16u && b->B >= 4u * lanes_l && bpc_s > bpc_l;
         chunk = large_fits && !throughput ? ENV_CHUNK_LARGE : ENV_CHUNK_SMALL;
@@ -92,7 +93,7 @@ static EnvPlan env_plan(const pbn_batch* b, const pbn_envcfg* cfg, int replay, u
             chunk = (uint32_t)k.env_chunk;
         bpc = chunk == ENV_CHUNK_LARGE ? bpc_l : bpc_s;
     } else {
-        p.error = max_blocks_env(b->W, b->net->kind, mode, grp, img, &bpc, b->net->N);
+        p.error = max_blocks_env(b->W, b->net->kind, mode, grp, img, &bpc);
     }
     if (k.env_bpc) bpc = std::min(bpc, k.env_bpc);
     p.tail_max = k.env_tail >= 0 ? (uint32_t)k.env_tail : ENV_TAIL_DEFAULT;
@@ -100,7 +101,7 @@ static EnvPlan env_plan(const pbn_batch* b, const pbn_envcfg* cfg, int replay, u
     // wave at a time -- every wave resolves its env 64 updates per block and takes the next from the
     // queue when it is done (PBNSIM_ENV_LANES overrides; 64 = lane mode, the tail at the end)
     p.lane_limit = 64u;
-    if (mode == 4) {
+    if (mode == ENV_MODE_TAIL) {
         const uint64_t slots = (uint64_t)b->n_cu * (uint64_t)bpc * (ENV_BLOCK / 64);
         if (k.env_lane_limit > 0)
             p.lane_limit = (uint32_t)k.env_lane_limit;
@@ -113,17 +114,17 @@ static EnvPlan env_plan(const pbn_batch* b, const pbn_envcfg* cfg, int replay, u
     // PBNSIM_ENV_GRID: exactly that many workgroups (at most the resident count; persistent waves: any grid
     // drains the counter, and surplus workgroups find the queue empty)
     if (k.env_grid_cap) p.grid = std::min(k.env_grid_cap, b->n_cu * bpc);
-    // tail hand-off (k_env mode 4): a wave holding several envs in tail mode passes envs it has not
+    // tail hand-off (k_env ENV_MODE_TAIL): a wave holding several envs in tail mode passes envs it has not
     // started on to idle waves of its workgroup (LDS). One lane per wave taking envs (small batches)
     // never holds two: off there
-    p.handoff = mode == 4 && k.env_steal && p.tail_max >= 1u && p.lane_limit >= 2u;
+    p.handoff = mode == ENV_MODE_TAIL && k.env_steal && p.tail_max >= 1u && p.lane_limit >= 2u;
     p.gpool = p.handoff && (k.env_grid_steal > 0 || (k.env_grid_steal < 0 && (cap >= GPOOL_MIN_CAP || n_calls > 1u)));
     p.mode = mode;
     p.grp = grp;
     p.erec_shift = erec_shift;
     p.chunk = chunk;
     p.bpc = bpc;
-    p.kernel = replay ? std::min(mode, 1) : mode;
+    p.kernel = replay ? std::min(mode, (int)ENV_MODE_COUNTERS) : mode;
     return p;
 }
 
@@ -170,7 +171,7 @@ static int env_launch(pbn_batch* b, pbn_envcfg* cfg, const EnvPlan& p, const Env
     a.fast = p.mode;
     a.grp = p.grp;
     a.chunk = p.chunk;
-    a.off_gen = p.mode == 3 ? cfg->L.bytes : cfg->L.bytes + p.erec_shift + 8u * (uint32_t)b->W * ENV_BLOCK;
+    a.off_gen = p.mode == ENV_MODE_GROUP ? cfg->L.bytes : cfg->L.bytes + p.erec_shift + 8u * (uint32_t)b->W * ENV_BLOCK;
     if (int rc = b->r6.counter.ensure(8)) return rc;
     a.counter = (unsigned long long*)b->r6.counter.p;
     a.n_cubes = cfg->H;

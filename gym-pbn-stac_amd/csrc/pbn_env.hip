@@ -1,5 +1,6 @@
 // pbn_env.hip -- the R6 env-step kernel k_env (lane, cooperative-draw and tail modes) and the env-step
-// dispatch; group mode's kernel k_env_grp is in pbn_env_grp.hip.
+// dispatch; group mode's kernel k_env_grp is in pbn_group.hip. The words its waves share (hand-off box, control
+// words, ring control, stamp slots) are named in pbn_env_words.hpp.
 //
 // Mapping: one lane owns one env at a time, its state in the lane's column of LDS state planes; each
 // workgroup stages the network image into LDS once; 256-thread workgroups sized to what is resident,
@@ -13,6 +14,7 @@
 
 #include "pbn_device.hpp"
 #include "pbn_env_device.hpp"
+#include "pbn_env_words.hpp"
 #include "pbn_launch.hpp"
 #include "pbn_params.hpp"
 
@@ -20,8 +22,7 @@ namespace pbn {
 
 #ifdef PBN_STAMPS
 // Measurement builds only (tools/build_exp.sh -DPBN_STAMPS): per-wave s_memrealtime stamps (100 MHz).
-// k_env (cooperative-draw path): per wave, ENV_STAMPS words (tools/env_stamps.py reads them)
-constexpr int ENV_STAMPS = 40;
+// k_env (cooperative-draw path): per wave, ENV_STAMPS words (EnvStampSlot; tools/env_stamps.py reads them)
 __device__ uint64_t g_env_stamps[16384 * ENV_STAMPS];
 #endif
 
@@ -40,7 +41,7 @@ __device__ uint64_t g_env_stamps[16384 * ENV_STAMPS];
 // negation), and "some cube matches" is a zero-byte test -- a handful of VALU ops
 // per update. Otherwise the state is matched against every cube after a change.
 //
-// GEN (FAST == 2, or 4 with <= 4 cubes: one counter word; predictor-mix networks, Philox):
+// GEN (FAST == ENV_MODE_COOP, or ENV_MODE_TAIL with <= 4 cubes: one counter word; predictor-mix networks, Philox):
 // before each chunk the whole wave
 // generates the chunk's draws for all its active lanes -- assignment k of
 // n_active * ENV_CHUNK goes to lane k % 64 -- and stores (node, chosen predictor) as
@@ -57,9 +58,6 @@ constexpr uint32_t ENV_OWN_DRAWS_MIN = PBN_ENV_OWN_DRAWS_MIN;  // active lanes f
 #define PBN_HELP_SLEEP 1  // a tail helper's sleep (x 64 cycles) between polls of its ring's consumed count
 #endif
 constexpr uint32_t ENV_LONG_USED = 1024;  // tail mode: envs past this many updates are resolved longest-first
-// grid pool (k_env): global-address-space views, so agent-scope atomics lower to global_ (not flat_) sc1 accesses
-typedef __attribute__((address_space(1))) uint32_t gu32;
-typedef __attribute__((address_space(1))) unsigned long long gu64;
 #ifndef PBN_GPOOL_SLEEP
 #define PBN_GPOOL_SLEEP 32  // a workgroup waiting on the pool sleeps this x 64 cycles between polls
 #endif
@@ -80,20 +78,14 @@ struct RankMagic {
 };
 __constant__ constexpr RankMagic kRankMagic{};
 
-// A wave's draw buffer (env_gen_wave_bytes(chunk)) in tail mode: the per-node 64-bit writer masks from
-// byte 0 (N <= 512 nodes: 4 KiB), the hand-off flag at chunk * 128 and the hand-off box (5 + 2W words)
-// 64 B after it; lane mode's draw table [chunk][64] u16 and counter table use the same bytes
-static_assert(8u * 512u <= ENV_CHUNK_SMALL * 128u, "tail writer masks (N <= 512) overlap the hand-off flag");
-static_assert(ENV_CHUNK_SMALL * 128u + 64u + 8u * (5u + 2u * 8u) <= env_gen_wave_bytes(ENV_CHUNK_SMALL),
-              "the hand-off box (W <= 8) overflows the wave's draw buffer");
 static_assert(ENV_CHUNK_SMALL % 8u == 0 && ENV_CHUNK_LARGE % 8u == 0 && ENV_UNROLL == 8u,
               "draw-round chunks: multiples of the unroll (and of 4: the own-draw iteration)");
 
 template <int W, int KIND, int REPLAY, int FAST>
 __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) void k_env(EnvArgs a) {
-    constexpr bool GEN = FAST == 2 || FAST == 4;
-    constexpr bool ONE_WORD = FAST == 4;  // <= 4 cubes: the high counter word is never read
-    constexpr bool TAIL = FAST == 4;      // wave-wide tail mode (see below)
+    constexpr bool GEN = FAST == ENV_MODE_COOP || FAST == ENV_MODE_TAIL;
+    constexpr bool ONE_WORD = FAST == ENV_MODE_TAIL;  // <= 4 cubes: the high counter word is never read
+    constexpr bool TAIL = FAST == ENV_MODE_TAIL;      // wave-wide tail mode (see below)
     static_assert(!GEN || (KIND == KIND_PREDICTOR_MIX && !REPLAY), "GEN: predictor mix, Philox");
     extern __shared__ __align__(16) uint8_t lds[];
 #ifdef PBN_STAMPS
@@ -145,19 +137,19 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
     const uint32_t CH = GEN ? a.chunk : ENV_CHUNK;
     const uint32_t GWB = env_gen_wave_bytes(CH);
     uint32_t* const wctl = reinterpret_cast<uint32_t*>(lds + a.off_gen + (ENV_BLOCK / 64) * GWB);
-    // grid pool words: device memory, every access a global agent-scope atomic (sc1: past the CU's L1)
+    // grid pool control words (PoolCtl)
     auto gctl = [&](int k) { return (gu32*)(a.gpool_ctl + k); };
     const bool GRID = TAIL && a.steal_local && a.gpool_cap != 0u;
     if (TAIL && a.steal_local && threadIdx.x == 0) {
-        wctl[0] = ENV_BLOCK / 64;  // busy
-        wctl[1] = 0u;          // idle mask
-        wctl[2] = 0u;          // grid pool: a wave of this workgroup is waiting on a ticket
-        wctl[3] = 0u;          // grid pool: 1 the launch's work is done, leave; 2 this workgroup left its CU's count
+        wctl[WCTL_BUSY] = ENV_BLOCK / 64;
+        wctl[WCTL_IDLE] = 0u;
+        wctl[WCTL_WAITING] = 0u;
+        wctl[WCTL_POOL] = 0u;
         if (GRID) {
             // this workgroup counts as live from its start (a workgroup dispatched late counts from then: a
             // ticket holder that saw the count at 0 gave its slot up, so no env can be pushed to it), and as
             // working on its CU until it first runs out of work
-            (void)__hip_atomic_fetch_add(gctl(2), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            (void)__hip_atomic_fetch_add(gctl(GCTL_LIVE), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             (void)__hip_atomic_fetch_add(gctl(GPOOL_CU_WORD + __smid()), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
@@ -165,15 +157,10 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
     __syncthreads();
     const PlaneT<ENV_BLOCK> P{reinterpret_cast<uint32_t*>(lds + a.L.bytes + a.erec_shift) + threadIdx.x};
 #ifdef PBN_STAMPS
-    // 0 start, 1 first chunk below ENV_OWN_DRAWS_MIN active lanes, 2 first chunk after a lane of the
-    // wave found the work queue empty,
-    // 3/4/5/6 first chunk with <= 32 / 16 / 8 / 2 active lanes, 7 end; 8 chunks, 9 sum of active
-    // lanes over chunks, 10 chunks in the tail (queue empty), 11 sum of active lanes there,
-    // 12 block, 13 hw id, 14 env steps of the wave that hit the update cap
     uint64_t est[ENV_STAMPS] = {};
     uint32_t ncapped = 0;
-    est[0] = __builtin_amdgcn_s_memrealtime();
-    est[33] = rt_entry;  // kernel entry (before the image is staged); est[0] is after the staging barrier
+    est[EST_START] = __builtin_amdgcn_s_memrealtime();
+    est[EST_ENTRY] = rt_entry;
 #endif
     const uint64_t* cubes = reinterpret_cast<const uint64_t*>(lds + a.off_cubes);
     const uint64_t* target = reinterpret_cast<const uint64_t*>(lds + a.off_target);
@@ -217,14 +204,14 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
     auto claim_idle = [&](uint32_t n) -> uint32_t {
         uint32_t claimed = 0;
         if (lane == 0) {
-            uint32_t idle = ldl(&wctl[1]);
+            uint32_t idle = ldl(&wctl[WCTL_IDLE]);
             n = min((uint32_t)__popc(idle), n);
             while (idle != 0u && n != 0u) {
                 const uint32_t w = (uint32_t)__ffs(idle) - 1u, bit = 1u << w;
                 idle &= ~bit;
                 // acquire: the claimed wave cleared its flag before setting its idle bit (release), so
                 // the flag / box writes that follow are ordered after that clear
-                if (__hip_atomic_fetch_and(&wctl[1], ~bit, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) & bit) {
+                if (__hip_atomic_fetch_and(&wctl[WCTL_IDLE], ~bit, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) & bit) {
                     claimed |= bit;
                     --n;
                 }
@@ -235,8 +222,7 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
     // ---- tail helpers (TAIL, EnvArgs::tail_helpers): the ring a long tail session's blocks are prepared
     // into, in the SESSION wave's draw buffer after its writer-mask table (the session wave, resolving
     // only, does no writer rounds of its own): ring_R slots of one uint2 per lane per block, then the
-    // control words -- tags [8] (block index held by each slot), [8] cons (blocks below it are consumed),
-    // [9] stop, [10] helpers' acks, [12] u0, [13] c1, [14]/[15] gid, [16] first ring block, [17] helpers
+    // control words (RingCtl)
     const uint32_t wm_bytes = ((N + 31u) >> 5) * 256u;
     // ring blocks are 128 updates (two per lane: 16 B per lane, 1 KiB per slot). The ring may run over the
     // session wave's own hand-off flag and box: those are unused while it is in a session (it clears its flag
@@ -246,7 +232,6 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
                                 ? min(8u, (GWB - wm_bytes - 96u) / 1024u) : 0u;
     auto ring_of = [&](uint32_t w) { return lds + a.off_gen + w * GWB + wm_bytes; };
     auto rctl_of = [&](uint32_t w) { return reinterpret_cast<uint32_t*>(ring_of(w) + ring_R * 1024u); };
-    constexpr uint64_t HELP_MARK = 0xFFFFFFFFFFFFFFFEull;  // box[0] of a wave recruited as a helper
     bool helping = false;
     uint32_t help_req = 0;  // session wave | helper index << 8
     auto local_push = [&](uint64_t cand) {
@@ -261,30 +246,18 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
                 uint32_t c = claimed;
                 for (uint32_t r = 0; r < above; ++r) c &= c - 1u;
                 tw = (uint32_t)__ffs(c) - 1u;
-                uint64_t* box = box_of(tw);
-                uint64_t s[W];
-                from_plane<W>(P, s);
-                box[0] = (uint64_t)e;
-                box[1] = (uint64_t)nst;
-                box[2] = (uint64_t)t | (uint64_t)used << 32;
-                box[3] = (uint64_t)m_lo | (hit0 ? 1ull << 32 : 0ull);
-                box[4] = (uint64_t)(int64_t)n_act;
-#pragma unroll
-                for (int k2 = 0; k2 < W; ++k2) {
-                    box[5 + k2] = o0[k2];
-                    box[5 + W + k2] = s[k2];
-                }
+                box_pack<W>(box_of(tw), P, e, nst, t, used, m_lo, hit0, n_act, o0);
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             if (mine) {
-                (void)__hip_atomic_fetch_add(&wctl[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                (void)__hip_atomic_fetch_add(&wctl[WCTL_BUSY], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 __hip_atomic_store(flag_of(tw), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 e = -1;
                 exhausted = true;
             }
-            if (lane == 0) atomicAdd(a.steal_count, k);  // diagnostics (pbn_env_handoffs)
+            if (lane == 0) atomicAdd(a.steal_count + STEAL_ENVS, k);  // diagnostics (pbn_env_handoffs)
 #ifdef PBN_STAMPS
-            est[16] += k;
+            est[EST_PUSHED] += k;
 #endif
         }
     };
@@ -294,14 +267,13 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
     // and writes one env into each -- the hand-off box's words as 8-B {epoch, value} granules, each one
     // aligned write-through store, so a slot is complete when every granule carries this launch's epoch (no
     // flag, no fence; MI355X_MICROARCH.md "granules"). A slot is claimed by an atomic max on its state word
-    // (epoch << 2 | 1) before it is written; a ticket holder that finds the live count at 0 (no workgroup
-    // working, no env in the pool) gives its slot up by a max to epoch << 2 | 2 -- whichever lands first
+    // (epoch << 2 | SLOT_CLAIMED) before it is written; a ticket holder that finds the live count at 0 (no workgroup
+    // working, no env in the pool) gives its slot up by a max to epoch << 2 | SLOT_GIVEN_UP -- whichever lands first
     // tells the other (a late push sees the slot given up and keeps its env; a holder that sees it claimed
     // waits for the granules). Epochs only grow between the pool's zeroings, so older states never match.
     // The waiting wave's siblings stay idle in LDS, so an env received this way gets tail helpers too.
     // Bit-exact like the workgroup hand-off: an env's draws are keyed by its global id, not by the wave.
-    constexpr uint32_t NBW = 2u * (5u + 2u * (uint32_t)W);  // hand-off words (u32) per env
-    static_assert(NBW <= GPOOL_GRANULES && NBW <= 64u, "grid pool slot: one granule per lane");
+    constexpr uint32_t NBW = box_nbw(W);  // hand-off words (u32) per env
     const uint32_t GE = a.gpool_epoch & 0x3FFFFFFFu;
     // The pool as this wave last saw it -- [0] tickets taken, [1] slots reserved, loaded into LDS by an
     // asynchronous LDS-DMA load (global_load_lds, sc1) issued at the previous look, so looking costs no round
@@ -330,31 +302,20 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
             int ok = 0;
             uint32_t sl = 0;
             if (lane == 0) {
-                (void)__hip_atomic_fetch_add(gctl(2), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // live first
-                sl = __hip_atomic_fetch_add(gctl(0), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                (void)__hip_atomic_fetch_add(gctl(GCTL_LIVE), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // live first
+                sl = __hip_atomic_fetch_add(gctl(GCTL_RESERVED), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if (sl < a.gpool_cap)
-                    ok = (__hip_atomic_fetch_max((gu32*)(a.gpool_state + sl), GE << 2 | 1u, __ATOMIC_RELAXED,
+                    ok = (__hip_atomic_fetch_max((gu32*)(a.gpool_state + sl), GE << 2 | SLOT_CLAIMED, __ATOMIC_RELAXED,
                                                  __HIP_MEMORY_SCOPE_AGENT) >> 2) != GE;
                 // given up by its ticket holder, or past the pool: the env stays here
-                (void)__hip_atomic_fetch_add(ok ? gctl(3) : gctl(2), ok ? 1u : 0xFFFFFFFFu, __ATOMIC_RELAXED,
+                (void)__hip_atomic_fetch_add(ok ? gctl(GCTL_PUSHED) : gctl(GCTL_LIVE), ok ? 1u : 0xFFFFFFFFu, __ATOMIC_RELAXED,
                                              __HIP_MEMORY_SCOPE_AGENT);
             }
             if (!__shfl(ok, 0)) return;
             sl = (uint32_t)__shfl((int)sl, 0);
             uint64_t* box = box_of(wv_in_wg);
             if (lane == (uint32_t)__ffsll((unsigned long long)cand) - 1u) {
-                uint64_t s[W];
-                from_plane<W>(P, s);
-                box[0] = (uint64_t)e;
-                box[1] = (uint64_t)nst;
-                box[2] = (uint64_t)t | (uint64_t)used << 32;
-                box[3] = (uint64_t)m_lo | (hit0 ? 1ull << 32 : 0ull);
-                box[4] = (uint64_t)(int64_t)n_act;
-#pragma unroll
-                for (int k2 = 0; k2 < W; ++k2) {
-                    box[5 + k2] = o0[k2];
-                    box[5 + W + k2] = s[k2];
-                }
+                box_pack<W>(box, P, e, nst, t, used, m_lo, hit0, n_act, o0);
                 e = -1;
                 exhausted = true;
             }
@@ -378,22 +339,22 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
         uint32_t ticket = 0;
         int leave = 0;
         if (lane == 0) {
-            (void)__hip_atomic_fetch_add(gctl(2), 0xFFFFFFFFu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            (void)__hip_atomic_fetch_add(gctl(GCTL_LIVE), 0xFFFFFFFFu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             gu32* cu = gctl(GPOOL_CU_WORD + __smid());
-            if ((ldl(&wctl[3]) & 2u) == 0u) {  // the first time this workgroup runs out of work
-                __hip_atomic_store(&wctl[3], 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if ((ldl(&wctl[WCTL_POOL]) & WG_LEFT_CU) == 0u) {  // the first time this workgroup runs out of work
+                __hip_atomic_store(&wctl[WCTL_POOL], WG_LEFT_CU, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 (void)__hip_atomic_fetch_add(cu, 0xFFFFFFFFu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             const uint64_t ta = __builtin_amdgcn_s_memrealtime();
             while (a.gpool_cu_idle && __hip_atomic_load(cu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) {
-                if (__hip_atomic_load(gctl(2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u ||
+                if (__hip_atomic_load(gctl(GCTL_LIVE), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u ||
                     __builtin_amdgcn_s_memrealtime() - ta > GPOOL_GIVE_UP_TICKS) {
                     leave = 1;  // (no ticket taken yet: nothing to give up)
                     break;
                 }
                 __builtin_amdgcn_s_sleep(PBN_GPOOL_SLEEP);
             }
-            if (!leave) ticket = __hip_atomic_fetch_add(gctl(1), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (!leave) ticket = __hip_atomic_fetch_add(gctl(GCTL_TICKETS), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         if (__shfl(leave, 0)) return false;
         ticket = (uint32_t)__shfl((int)ticket, 0);
@@ -403,6 +364,11 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
         gu64* g = (gu64*)(a.gpool + (uint64_t)ticket * GPOOL_GRANULES);
         const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
         bool claimed = false;  // the quiet give-up found the slot claimed: its words are on their way
+        // the give-up: true when it stands (leave); false: a push had claimed the slot, its words are on their way
+        auto give_up = [&]() {
+            return (__hip_atomic_fetch_max((gu32*)(a.gpool_state + ticket), GE << 2 | SLOT_GIVEN_UP, __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_AGENT) >> 2) != GE;
+        };
         for (uint32_t it = 0;; ++it) {
             // lane 0 polls the slot's last granule; once it carries the epoch, the whole wave sweeps the slot
             int seen = 0;
@@ -423,24 +389,22 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
             if ((it & 1u) == 1u) {
                 int leave = 0;
                 if (lane == 0) {
-                    if (!claimed && __hip_atomic_load(gctl(2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
+                    if (!claimed && __hip_atomic_load(gctl(GCTL_LIVE), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
                         // nothing live: no push can come any more -- unless one already claimed this slot
-                        leave = (__hip_atomic_fetch_max((gu32*)(a.gpool_state + ticket), GE << 2 | 2u, __ATOMIC_RELAXED,
-                                                        __HIP_MEMORY_SCOPE_AGENT) >> 2) != GE;
+                        leave = give_up();
                         claimed = !leave;
                     }
                     const uint64_t waited = __builtin_amdgcn_s_memrealtime() - t0;
                     if (!leave && !claimed && waited > GPOOL_GIVE_UP_TICKS) {
                         // waited long with no env: give the slot up (as above) and leave, unless a push claimed it
-                        if ((__hip_atomic_fetch_max((gu32*)(a.gpool_state + ticket), GE << 2 | 2u, __ATOMIC_RELAXED,
-                                                    __HIP_MEMORY_SCOPE_AGENT) >> 2) != GE)
+                        if (give_up())
                             leave = 1;
                         else
                             claimed = true;
                     }
                     if (!leave && claimed && waited > GPOOL_TIMEOUT_TICKS) {
                         leave = 1;
-                        (void)__hip_atomic_fetch_add(gctl(4), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        (void)__hip_atomic_fetch_add(gctl(GCTL_TIMEOUTS), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         atomicOr(a.error, 2);
                         atomicOr(a.error + 1, 2);  // sticky: device-path launches report it at pbn_sync
                     }
@@ -454,7 +418,7 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
         if constexpr (TAIL) {
 #ifdef PBN_STAMPS
             const uint64_t t_in = __builtin_amdgcn_s_memrealtime();
-            if (!est[18]) est[18] = t_in;
+            if (!est[EST_FIRST_POP]) est[EST_FIRST_POP] = t_in;
 #endif
             int32_t got = 0;
             if (lane == 0) {
@@ -463,19 +427,19 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
                 // and the bit set with release semantics, so a pusher that claims the bit (its fetch_and
                 // reads it) cannot be ordered before the cleared flag
                 __hip_atomic_store(flag_of(wv_in_wg), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                (void)__hip_atomic_fetch_or(&wctl[1], bit, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-                (void)__hip_atomic_fetch_add(&wctl[0], 0xFFFFFFFFu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                (void)__hip_atomic_fetch_or(&wctl[WCTL_IDLE], bit, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                (void)__hip_atomic_fetch_add(&wctl[WCTL_BUSY], 0xFFFFFFFFu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 for (;;) {
                     if (ldl(flag_of(wv_in_wg)) != 0u) {
                         got = 1;
                         break;
                     }
-                    if (ldl(&wctl[0]) == 0u) {
+                    if (ldl(&wctl[WCTL_BUSY]) == 0u) {
                         if (GRID) {
                             // nobody busy: the launch is done (the waiting wave said so) -- leave with the idle
                             // bit set (no wave is busy to claim it); else one wave waits on a ticket for the
                             // workgroup (the others stay idle here)
-                            if (ldl(&wctl[3]) & 1u) {
+                            if (ldl(&wctl[WCTL_POOL]) & WG_DONE) {
                                 got = -1;
                                 break;
                             }
@@ -483,21 +447,21 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
                             // acquire: a sibling that got an env from the pool raised the busy count before it
                             // released this word, so the count re-read below sees it (the count
                             // read above may predate that increment)
-                            if (__hip_atomic_compare_exchange_strong(&wctl[2], &zero, 1u, __ATOMIC_ACQUIRE,
+                            if (__hip_atomic_compare_exchange_strong(&wctl[WCTL_WAITING], &zero, 1u, __ATOMIC_ACQUIRE,
                                                                      __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) {
-                                if (ldl(&wctl[0]) != 0u) {
+                                if (ldl(&wctl[WCTL_BUSY]) != 0u) {
                                     // the workgroup is busy again: not idle, keep polling
-                                    __hip_atomic_store(&wctl[2], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                                    __hip_atomic_store(&wctl[WCTL_WAITING], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                                     __builtin_amdgcn_s_sleep(2);
                                     continue;
                                 }
-                                if (__hip_atomic_fetch_and(&wctl[1], ~bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) &
+                                if (__hip_atomic_fetch_and(&wctl[WCTL_IDLE], ~bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) &
                                     bit) {
                                     got = 3;
                                     break;
                                 }
                                 // claimed meanwhile: an env or a helper request is on its way
-                                __hip_atomic_store(&wctl[2], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                                __hip_atomic_store(&wctl[WCTL_WAITING], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                                 while (ldl(flag_of(wv_in_wg)) == 0u) __builtin_amdgcn_s_sleep(1);
                                 got = 1;
                                 break;
@@ -507,7 +471,7 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
                             __builtin_amdgcn_s_sleep(PBN_GPOOL_SLEEP);
                         } else {
                             // nobody busy: leave, unless a pusher claimed this wave before the count reached 0
-                            if (__hip_atomic_fetch_and(&wctl[1], ~bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) & bit) {
+                            if (__hip_atomic_fetch_and(&wctl[WCTL_IDLE], ~bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) & bit) {
                                 got = -1;
                                 break;
                             }
@@ -525,45 +489,30 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
                 if (lane == 0) {
                     if (env) {
                         // busy before the ticket word is released: the siblings never see the workgroup idle
-                        (void)__hip_atomic_fetch_add(&wctl[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        __hip_atomic_store(&wctl[2], 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        (void)__hip_atomic_fetch_add(&wctl[WCTL_BUSY], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        __hip_atomic_store(&wctl[WCTL_WAITING], 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
                     } else {
-                        (void)__hip_atomic_fetch_or(&wctl[3], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        (void)__hip_atomic_fetch_or(&wctl[WCTL_POOL], WG_DONE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     }
                 }
                 got = env ? 1 : -1;
 #ifdef PBN_STAMPS
-                est[16] += env ? 0x10000u : 0u;  // envs received from the grid pool (high half)
+                est[EST_PUSHED] += env ? 0x10000u : 0u;  // envs received from the grid pool (high half)
 #endif
             }
 #ifdef PBN_STAMPS
-            est[17] += __builtin_amdgcn_s_memrealtime() - t_in;
-            est[15] += got > 0 ? 1u : 0u;
+            est[EST_POP_TICKS] += __builtin_amdgcn_s_memrealtime() - t_in;
+            est[EST_POPS] += got > 0 ? 1u : 0u;
 #endif
             if (got < 0) return 0;
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-            if (box_of(wv_in_wg)[0] == HELP_MARK) {  // recruited as a tail helper (every lane reads the box)
-                help_req = (uint32_t)box_of(wv_in_wg)[1];
+            if (box_of(wv_in_wg)[BOX_E] == HELP_MARK) {  // recruited as a tail helper (every lane reads the box)
+                help_req = (uint32_t)box_of(wv_in_wg)[HELP_REQ];
                 if (lane == 0) __hip_atomic_store(flag_of(wv_in_wg), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 return 2;
             }
             if (lane == 0) {
-                const uint64_t* box = box_of(wv_in_wg);
-                e = (int64_t)box[0];
-                nst = (int64_t)box[1];
-                const uint64_t tu = box[2], mh = box[3];
-                t = (uint32_t)tu;
-                used = (uint32_t)(tu >> 32);
-                m_lo = (uint32_t)mh;
-                hit0 = ((mh >> 32) & 1ull) != 0ull;
-                n_act = (int)(int64_t)box[4];
-                uint64_t s[W];
-#pragma unroll
-                for (int k2 = 0; k2 < W; ++k2) {
-                    o0[k2] = box[5 + k2];
-                    s[k2] = box[5 + W + k2];
-                }
-                to_plane<W>(P, s);
+                box_unpack<W>(box_of(wv_in_wg), P, e, nst, t, used, m_lo, hit0, n_act, o0);
                 capped = false;
                 __hip_atomic_store(flag_of(wv_in_wg), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
@@ -664,17 +613,17 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
             const uint64_t now = __builtin_amdgcn_s_memrealtime();
             const uint32_t na = (uint32_t)__popcll(act);
             const bool qe = __ballot(exhausted) != 0;  // a lane of this wave found the queue empty
-            if (!est[1] && na < ENV_OWN_DRAWS_MIN) est[1] = now;
-            if (!est[2] && qe) est[2] = now;
-            if (!est[3] && na <= 32) est[3] = now;
-            if (!est[4] && na <= 16) est[4] = now;
-            if (!est[5] && na <= 8) est[5] = now;
-            if (!est[6] && na <= 2) est[6] = now;
-            est[8] += 1;
-            est[9] += na;
+            if (!est[EST_BELOW_OWN] && na < ENV_OWN_DRAWS_MIN) est[EST_BELOW_OWN] = now;
+            if (!est[EST_QUEUE_EMPTY] && qe) est[EST_QUEUE_EMPTY] = now;
+            if (!est[EST_LE32] && na <= 32) est[EST_LE32] = now;
+            if (!est[EST_LE16] && na <= 16) est[EST_LE16] = now;
+            if (!est[EST_LE8] && na <= 8) est[EST_LE8] = now;
+            if (!est[EST_LE2] && na <= 2) est[EST_LE2] = now;
+            est[EST_CHUNKS] += 1;
+            est[EST_ACTIVE_SUM] += na;
             if (qe) {
-                est[10] += 1;
-                est[11] += na;
+                est[EST_TAIL_CHUNKS] += 1;
+                est[EST_TAIL_ACTIVE] += na;
             }
         }
 #endif
@@ -729,29 +678,25 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
                 // takes the session's update base, call index and env id from the session wave's ring control
                 auto from_L = [&](uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)L); };
                 const uint32_t* hrc = rctl_of(help_req & 0xFFu);
-                uint32_t u = helping ? hrc[12] : from_L(used);
+                uint32_t u = helping ? hrc[RING_U0] : from_L(used);
                 uint32_t m = from_L(m_lo);
                 const uint32_t h0 = from_L(hit0 ? 1u : 0u);
-                const uint64_t gid = helping ? ((uint64_t)hrc[15] << 32 | hrc[14])
+                const uint64_t gid = helping ? ((uint64_t)hrc[RING_GID_HI] << 32 | hrc[RING_GID_LO])
                                              : a.env_base + ((uint64_t)from_L((uint32_t)((uint64_t)e >> 32)) << 32 |
                                                              (uint64_t)from_L((uint32_t)(uint64_t)e));
-                const uint32_t c1 = helping ? hrc[13] : a.call_idx + from_L(t);
+                const uint32_t c1 = helping ? hrc[RING_C1] : a.call_idx + from_L(t);
                 uint32_t* col = P.base + ((int32_t)L - (int32_t)lane);  // lane L's plane column
                 const uint8_t* colb = reinterpret_cast<const uint8_t*>(col);
                 const uint4* erec = reinterpret_cast<const uint4*>(lds + a.L.off_rec);
                 uint8_t* const wmc = reinterpret_cast<uint8_t*>(wm);
                 const uint64_t below = (1ull << lane) - 1ull, upto = (2ull << lane) - 1ull;
-                // predictor choice on the draw word (compact u32 thresholds, rows of tp4 <= 16: mode 2/4
+                // predictor choice on the draw word (compact u32 thresholds, rows of tp4 <= 16: ENV_MODE_COOP / _TAIL
                 // needs <= 16 predictors per node), as guarded straight-line reads rather than a loop
                 const uint32_t nq = X.tp4 >> 2;
                 auto tail_session = [&](auto one_row) {
                 // one_row: every node's thresholds fit one 16-B row (<= 5 predictors: Bittner-200), so a
                 // choice is one ds_read_b128 and the two choices of a Philox pair issue back to back
                 constexpr bool ONE_ROW = decltype(one_row)::value;
-                auto cnt4 = [](const uint4& t4, uint32_t a32) {
-                    return (a32 >= t4.x ? 1u : 0u) + (a32 >= t4.y ? 1u : 0u) + (a32 >= t4.z ? 1u : 0u) +
-                           (a32 >= t4.w ? 1u : 0u);
-                };
                 auto choice = [&](uint32_t i, uint32_t a32) -> uint32_t {
                     const uint4* thr = reinterpret_cast<const uint4*>(lds) + (ONE_ROW ? i : i * nq);
                     uint32_t j = cnt4(thr[0], a32);
@@ -812,17 +757,31 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
                 // k + 3's draw issued while k resolves): a lone chain 0.0156 vs 0.0155 us per update, and
                 // 2-5 more VGPRs spilled in the lane-mode path (the kernel is at its 128-VGPR bound).
                 const uint32_t u0 = u;
-                auto draw_idx = [&](uint32_t b) -> uint32_t {  // block b's env-record index
+                // block b's draw (stageA: node, record row, choice word; with one row per node its thresholds too)
+                // and the env record its choice selects (stageB)
+                struct StA {
+                    uint32_t i, ir, a32;
+                    uint4 t4;
+                };
+                auto stageA = [&](uint32_t b) {
                     const uint32_t U = u0 + 64u * b + lane;
                     uint32_t w4[4];
                     draw(U >> 1, w4);
                     const uint32_t odd = U & 1u;
-                    const uint32_t i = philox_node<KIND>(odd ? w4[2] : w4[0], N);
-                    uint32_t ir = __umul24(i, X.rs);
-                    asm volatile("" : "+v"(ir));  // else folded with the choice into a quarter-rate v_mad_u64_u32
-                    return ir + choice(i, odd ? w4[3] : w4[1]);
+                    StA A;
+                    A.i = philox_node<KIND>(odd ? w4[2] : w4[0], N);
+                    A.ir = __umul24(A.i, X.rs);
+                    asm volatile("" : "+v"(A.ir));  // else folded with the choice into a quarter-rate v_mad_u64_u32
+                    A.a32 = odd ? w4[3] : w4[1];
+                    if constexpr (ONE_ROW) A.t4 = reinterpret_cast<const uint4*>(lds)[A.i];
+                    return A;
                 };
-                auto erec_of = [&](uint32_t E) { return erec[E & 0xFFFFu]; };
+                auto stageB = [&](const StA& A) {
+                    if constexpr (ONE_ROW)
+                        return erec[(A.ir + cnt4(A.t4, A.a32)) & 0xFFFFu];
+                    else
+                        return erec[(A.ir + choice(A.i, A.a32)) & 0xFFFFu];
+                };
                 // Writer round of a block (its records q): node n's 64-bit writer mask at wmc + 8n, n = plane
                 // offset / 32 | bit (offset = dword * 4 ENV_BLOCK); or, read the four operands' masks, clear.
                 struct WRound {
@@ -878,7 +837,7 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
                 bool fin = false, hitf = false;
                 uint32_t nblk = 0;
                 auto prepare = [&](uint32_t b) {
-                    const uint4 qb = erec_of(draw_idx(b));
+                    const uint4 qb = stageB(stageA(b));
                     return writers(qb, wround(qb));
                 };
                 // The next block's preparation in three stages placed between the current block's own, so
@@ -887,24 +846,6 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
                 // ahead of them (one-row thresholds, one Philox call per lane): lone tail launch 57.9 -> 56.6 us,
                 // 131,072 envs per step at cap 2^20 2.11 -> 2.05 ms (profiles/r04_r6_tail_split_ab.json)
                 constexpr bool SPLIT = ONE_ROW;
-                struct StA {
-                    uint32_t ir, a32;
-                    uint4 t4;
-                };
-                auto stageA = [&](uint32_t b) {
-                    const uint32_t U = u0 + 64u * b + lane;
-                    uint32_t w4[4];
-                    draw(U >> 1, w4);
-                    const uint32_t odd = U & 1u;
-                    const uint32_t i = philox_node<KIND>(odd ? w4[2] : w4[0], N);
-                    StA A;
-                    A.ir = __umul24(i, X.rs);
-                    asm volatile("" : "+v"(A.ir));
-                    A.a32 = odd ? w4[3] : w4[1];
-                    A.t4 = reinterpret_cast<const uint4*>(lds)[i];
-                    return A;
-                };
-                auto stageB = [&](const StA& A) { return erec[(A.ir + cnt4(A.t4, A.a32)) & 0xFFFFu]; };
                 if constexpr (ONE_ROW) {
                     if (helping) {
                         // ---- tail helper: ring blocks hj, hj + H, ... of the session wave's env. A ring block is
@@ -919,7 +860,7 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
                         const uint32_t sw = help_req & 0xFFu, hj = (help_req >> 8) & 0xFFu;
                         uint8_t* const ring = ring_of(sw);
                         uint32_t* const rcw = rctl_of(sw);
-                        const uint32_t H = rcw[17];
+                        const uint32_t H = rcw[RING_HELPERS];
                         // zero the 128-bit table (its upper half may hold this wave's own old ring slots)
                         for (uint32_t q2 = lane; q2 < wm_bytes / 8u; q2 += 64u)
                             reinterpret_cast<uint4*>(wmc)[q2] = make_uint4(0u, 0u, 0u, 0u);
@@ -947,11 +888,11 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
                         for (uint32_t jb = hj;; jb += H) {
                             bool stop = false;
                             for (;;) {
-                                if (ldl(&rcw[9]) != 0u) {
+                                if (ldl(&rcw[RING_STOP]) != 0u) {
                                     stop = true;
                                     break;
                                 }
-                                if (jb < ldl(&rcw[8]) + ring_R) break;
+                                if (jb < ldl(&rcw[RING_CONS]) + ring_R) break;
                                 __builtin_amdgcn_s_sleep(PBN_HELP_SLEEP);
                             }
                             if (stop) break;
@@ -988,12 +929,12 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
                             reinterpret_cast<uint4*>(ring + slot * 1024u)[lane] =
                                 make_uint4(idxe | (idxo << 16), hme | (hmo << 4) | (nxe << 8) | (nxo << 16), rre, rro);
                             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                            if (lane == 0) __hip_atomic_store(&rcw[slot], jb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                            if (lane == 0) __hip_atomic_store(&rcw[RING_TAGS + slot], jb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                             slot += H;
                             if (slot >= ring_R) slot -= ring_R;
                         }
                         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                        if (lane == 0) (void)__hip_atomic_fetch_add(&rcw[10], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        if (lane == 0) (void)__hip_atomic_fetch_add(&rcw[RING_ACKS], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                         helping = false;
                         return;
                     }
@@ -1013,13 +954,7 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
                 auto blocks = [&]() {
                 for (; !fin; ++k) {
 #ifdef PBN_STAMPS
-                    // tail block phases (shader clocks, s_memtime): 19 blocks, 20 cycles per block, 21 fixed-point
-                    // rounds, 22 cycles of the resolution (fixed point), 23 cycles from the block's top to the
-                    // later blocks' stages issued, 24..31 blocks by rounds (0..6, 7+)
-                    const uint64_t c_top = __builtin_amdgcn_s_memtime();
-                    const uint64_t r_top = __builtin_amdgcn_s_memrealtime();  // 100 MHz: calibrates s_memtime
-                    if (!est[34]) est[34] = r_top;
-                    uint32_t nround = 0;
+                    BlockClocks bc = stamp_block_top(est);  // tail block phases (EST_TB_*)
 #endif
                     const uint4 q = D.q;
                     const uint32_t U = u + lane;
@@ -1037,7 +972,7 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
                     else
                         Dn = prepare(k + 1u);
 #ifdef PBN_STAMPS
-                    const uint64_t c_prep = __builtin_amdgcn_s_memtime();
+                    bc.c_prep = __builtin_amdgcn_s_memtime();
 #endif
                     const uint32_t v3 = __builtin_amdgcn_ubfe(b3, ss, 1);
                     const uint32_t p0 = (__builtin_amdgcn_ubfe(b0, q.z, 1) << 3) | (__builtin_amdgcn_ubfe(b1, q.z >> 8, 1) << 2) |
@@ -1052,7 +987,7 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
                     uint32_t x3;
                     auto fround = [&](uint32_t yy) {
 #ifdef PBN_STAMPS
-                        ++nround;
+                        ++bc.nround;
 #endif
                         const uint64_t Y = __ballot(yy != 0u);
                         const uint32_t p = pf | (((uint32_t)(Y >> r0) & k0) << 3) | (((uint32_t)(Y >> r1) & k1) << 2) |
@@ -1069,7 +1004,7 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
                     y = yn;
                     if constexpr (SPLIT) qn = stageB(An);
 #ifdef PBN_STAMPS
-                    const uint64_t c_fp = __builtin_amdgcn_s_memtime();
+                    bc.c_fp = __builtin_amdgcn_s_memtime();
 #endif
                     // packed counter deltas (+ d for 0 -> 1, - d for 1 -> 0), prefix over the block
                     const uint32_t sg = y - 1u;
@@ -1091,18 +1026,7 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
                     else
                         D = Dn;  // (the commit above and the next block's plane reads stay in issue order)
 #ifdef PBN_STAMPS
-                    {
-                        const uint64_t c_end = __builtin_amdgcn_s_memtime();
-                        const uint64_t r_end = __builtin_amdgcn_s_memrealtime();
-                        est[32] += r_end - r_top;  // realtime ticks (10 ns) in tail blocks
-                        est[35] = r_end;
-                        est[19] += 1;
-                        est[20] += c_end - c_top;
-                        est[21] += nround;
-                        est[22] += c_fp - c_prep;
-                        est[23] += c_prep - c_top;
-                        est[24 + min(nround, 7u)] += 1;
-                    }
+                    stamp_block_end(est, bc);
 #endif
                     // every 16 blocks: idle waves may have appeared since this env was started -- they take
                     // this wave's unstarted envs first, then (a long session: >= 16 blocks) up to three of
@@ -1111,7 +1035,7 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
                     if (a.steal_local && (++nblk & 15u) == 0u && !fin) {
                         const uint64_t others = __ballot(e >= 0) & ~(1ull << L);
                         if (others) local_push(others);
-                        const bool alone = !(SPLIT && a.tail_helpers && ring_R >= 3u && ldl(&wctl[1]) != 0u);
+                        const bool alone = !(SPLIT && a.tail_helpers && ring_R >= 3u && ldl(&wctl[WCTL_IDLE]) != 0u);
                         if (others) grid_push(__ballot(e >= 0) & ~(1ull << L));
                         // (a ring starts at an even update: helpers key a pair's Philox call by u >> 1 -- always so
                         // here, lane mode and the hand-offs start sessions at multiples of the draw chunk and a
@@ -1120,31 +1044,31 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
                             const uint32_t cl = claim_idle(min((uint32_t)a.tail_helpers, 3u));
                             if (cl) {
                                 const uint32_t H = (uint32_t)__popc(cl);
-                                if (lane < 8u) rcs[lane] = 0xFFFFFFFFu;  // tags: no block
+                                if (lane < 8u) rcs[RING_TAGS + lane] = 0xFFFFFFFFu;  // no block
                                 if (lane == 0) {
-                                    rcs[8] = 0u;   // cons: ring blocks consumed
-                                    rcs[9] = 0u;   // stop
-                                    rcs[10] = 0u;  // acks
-                                    rcs[12] = u;   // the ring's first update (even: a block boundary)
-                                    rcs[13] = c1;
-                                    rcs[14] = (uint32_t)gid;
-                                    rcs[15] = (uint32_t)(gid >> 32);
-                                    rcs[17] = H;
+                                    rcs[RING_CONS] = 0u;
+                                    rcs[RING_STOP] = 0u;
+                                    rcs[RING_ACKS] = 0u;
+                                    rcs[RING_U0] = u;
+                                    rcs[RING_C1] = c1;
+                                    rcs[RING_GID_LO] = (uint32_t)gid;
+                                    rcs[RING_GID_HI] = (uint32_t)(gid >> 32);
+                                    rcs[RING_HELPERS] = H;
                                 }
                                 uint32_t tw = 0;
                                 if (lane < H) {  // the lane-th claimed wave becomes helper `lane`
                                     uint32_t c = cl;
                                     for (uint32_t r = 0; r < lane; ++r) c &= c - 1u;
                                     tw = (uint32_t)__ffs(c) - 1u;
-                                    box_of(tw)[0] = HELP_MARK;
-                                    box_of(tw)[1] = (uint64_t)(wv_in_wg | (lane << 8));
+                                    box_of(tw)[BOX_E] = HELP_MARK;
+                                    box_of(tw)[HELP_REQ] = (uint64_t)(wv_in_wg | (lane << 8));
                                 }
                                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                                 if (lane < H) {
-                                    (void)__hip_atomic_fetch_add(&wctl[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                                    (void)__hip_atomic_fetch_add(&wctl[WCTL_BUSY], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                                     __hip_atomic_store(flag_of(tw), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                                 }
-                                if (lane == 0) atomicAdd(a.steal_count + 1, H);  // diagnostics (pbn_env_tail_helpers)
+                                if (lane == 0) atomicAdd(a.steal_count + STEAL_HELPERS, H);  // diagnostics (pbn_env_tail_helpers)
                                 ringH = H;
                                 return;  // on in ring128
                             }
@@ -1172,9 +1096,9 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
                         return v;
                     };
                     auto poll = [&](uint32_t jb, uint32_t sl) {
-                        if (ldl(&rcr[sl]) != jb) {
+                        if (ldl(&rcr[RING_TAGS + sl]) != jb) {
                             ++rwaits;  // diagnostics: the block's helper had not written it yet
-                            while (ldl(&rcr[sl]) != jb) __builtin_amdgcn_s_sleep(1);
+                            while (ldl(&rcr[RING_TAGS + sl]) != jb) __builtin_amdgcn_s_sleep(1);
                         }
                         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
                         // the slot's address from the control words' (the ring ends where they start), formed
@@ -1188,7 +1112,7 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
                     uint4 sC = poll(0u, 0u);
                     uint4 sN = poll(1u, nxt_slot(0u));
                     asm volatile("" ::"v"(sN.x), "v"(sN.w) : "memory");
-                    if (lane == 0) __hip_atomic_store(&rcr[8], 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    if (lane == 0) __hip_atomic_store(&rcr[RING_CONS], 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     uint32_t rsl = nxt_slot(nxt_slot(0u));  // slot of block j + 2
                     uint4 qe = erec[sC.x & 0xFFFFu], qo = erec[sC.x >> 16];
                     uint32_t nde = nd_of(qe), ndo = nd_of(qo), inf = sC.y, rre = sC.z, rro = sC.w;
@@ -1198,11 +1122,7 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
                     for (uint32_t jb = 0; !fin; ++jb) {
                         ++rblocks;
 #ifdef PBN_STAMPS
-                        // the same tail-block stamps as the self-prepared loop (est 19-31; rounds count fround calls)
-                        const uint64_t c_top = __builtin_amdgcn_s_memtime();
-                        const uint64_t r_top = __builtin_amdgcn_s_memrealtime();
-                        if (!est[34]) est[34] = r_top;
-                        uint32_t nround = 0;
+                        BlockClocks bc = stamp_block_top(est);  // tail block phases (EST_TB_*)
 #endif
                         const uint32_t se = qe.z >> 24, so = qo.z >> 24;
                         const uint32_t e0 = *reinterpret_cast<const uint32_t*>(colr + (qe.x & 0xFFFFu));
@@ -1217,7 +1137,7 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
                         const uint4 qe2 = erec[sN.x & 0xFFFFu], qo2 = erec[sN.x >> 16];
                         const uint4 sNN = poll(jb + 2u, rsl);
 #ifdef PBN_STAMPS
-                        const uint64_t c_prep = __builtin_amdgcn_s_memtime();
+                        bc.c_prep = __builtin_amdgcn_s_memtime();
 #endif
                         const uint32_t v3e = __builtin_amdgcn_ubfe(e3, se, 1), v3o = __builtin_amdgcn_ubfe(o3, so, 1);
                         const uint32_t p0e = (__builtin_amdgcn_ubfe(e0, qe.z, 1) << 3) | (__builtin_amdgcn_ubfe(e1, qe.z >> 8, 1) << 2) |
@@ -1229,7 +1149,7 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
                         uint32_t xe, xo;
                         auto fround = [&](uint32_t ye_, uint32_t yo_, uint32_t& yne, uint32_t& yno) {
 #ifdef PBN_STAMPS
-                            ++nround;
+                            ++bc.nround;
 #endif
                             const uint64_t Ye = __ballot(ye_ != 0u), Yo = __ballot(yo_ != 0u);
                             const uint32_t pe = pfe | ((look(Ye, Yo, rre & 255u) & (hme >> 3)) << 3) |
@@ -1256,11 +1176,11 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
                         ye = yne;
                         yo = yno;
 #ifdef PBN_STAMPS
-                        const uint64_t c_fp = __builtin_amdgcn_s_memtime();
+                        bc.c_fp = __builtin_amdgcn_s_memtime();
 #endif
                         // block j + 2's slot is in registers: it is free (the asm keeps the store after the read)
                         asm volatile("" ::"v"(sNN.x), "v"(sNN.w) : "memory");
-                        if (lane == 0) __hip_atomic_store(&rcr[8], jb + 3u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        if (lane == 0) __hip_atomic_store(&rcr[RING_CONS], jb + 3u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                         rsl = nxt_slot(rsl);
                         // packed counter deltas in update order: the pair's sum prefixed over the lanes
                         const uint32_t sge = ye - 1u, sgo = yo - 1u;
@@ -1296,18 +1216,7 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
                         rro = sN.w;
                         sN = sNN;
 #ifdef PBN_STAMPS
-                        {
-                            const uint64_t c_end = __builtin_amdgcn_s_memtime();
-                            const uint64_t r_end = __builtin_amdgcn_s_memrealtime();
-                            est[32] += r_end - r_top;
-                            est[35] = r_end;
-                            est[19] += 1;
-                            est[20] += c_end - c_top;
-                            est[21] += nround;
-                            est[22] += c_fp - c_prep;
-                            est[23] += c_prep - c_top;
-                            est[24 + min(nround, 7u)] += 1;
-                        }
+                        stamp_block_end(est, bc);
 #endif
                         // every 8 ring blocks (1,024 updates): idle waves may take this wave's unstarted envs
                         if ((jb & 7u) == 7u && !fin) {
@@ -1322,22 +1231,22 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
                     // release the helpers: stop, then wait until each has acknowledged (the ring lives in this
                     // wave's draw buffer, which its next session reuses)
                     if (lane == 0) {
-                        __hip_atomic_store(&rcs[9], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        while (ldl(&rcs[10]) != ringH) __builtin_amdgcn_s_sleep(1);
+                        __hip_atomic_store(&rcs[RING_STOP], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        while (ldl(&rcs[RING_ACKS]) != ringH) __builtin_amdgcn_s_sleep(1);
                     }
                     wave_sync();
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
                     if (lane == 0) {
-                        atomicAdd(a.steal_count + 2, rblocks);
-                        atomicAdd(a.steal_count + 3, rwaits);
+                        atomicAdd(a.steal_count + STEAL_RING_BLOCKS, rblocks);
+                        atomicAdd(a.steal_count + STEAL_RING_WAITS, rwaits);
                     }
                 }
 #ifdef PBN_STAMPS
-                if ((u - sess_u0) / 64u > est[37]) {  // the wave's longest session: start, blocks, end, prior updates
-                    est[36] = sess_rt;
-                    est[37] = (u - sess_u0) / 64u;
-                    est[38] = __builtin_amdgcn_s_memrealtime();
-                    est[39] = sess_u0;
+                if ((u - sess_u0) / 64u > est[EST_SESS_BLOCKS]) {  // the wave's longest session: start, blocks, end, prior updates
+                    est[EST_SESS_START] = sess_rt;
+                    est[EST_SESS_BLOCKS] = (u - sess_u0) / 64u;
+                    est[EST_SESS_END] = __builtin_amdgcn_s_memrealtime();
+                    est[EST_SESS_U0] = sess_u0;
                 }
 #endif
                 if (lane == L) {
@@ -1360,9 +1269,6 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
             uint8_t* gw = lds + a.off_gen + (threadIdx.x >> 6) * GWB;
             gbuf = reinterpret_cast<uint16_t*>(gw);                                   // [CH][64]
             uint4* ctr_tab = reinterpret_cast<uint4*>(gw + CH * 128 + 64);  // [64] by rank
-            auto cnt4 = [](const uint4& t4, uint32_t a32) {
-                return (a32 >= t4.x ? 1u : 0u) + (a32 >= t4.y ? 1u : 0u) + (a32 >= t4.z ? 1u : 0u) + (a32 >= t4.w ? 1u : 0u);
-            };
             const uint32_t nact = (uint32_t)__popcll(act);
             if (nact >= ENV_OWN_DRAWS_MIN) {
                 // (nearly) every lane active: each lane draws its own entries from its registers
@@ -1417,9 +1323,7 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
                 ctr_tab[__popcll(act & ((1ull << lane) - 1ull))] =
                     make_uint4(used >> 1, a.call_idx + t, (uint32_t)gid, ((uint32_t)(gid >> 32) & 0xFFFFFFu) | (lane << 24));
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_sync();
             const uint32_t total = nact * (CH / 2);  // pairs of updates: one Philox call each
             // k / nact as a multiply-high by ceil(2^32 / nact): exact for k < 2^16 (nact == 1 handled apart,
             // its multiplier 2^32 does not fit 32 bits)
@@ -1490,9 +1394,7 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
             else
                 rounds(std::false_type{}, 0u);
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_sync();
         }
         if (e < 0) continue;
 
@@ -1506,7 +1408,6 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
             // Entries, records and counter deltas do not depend on the state: the entry is read
             // three updates ahead, its EnvRec two ahead and the node's counter deltas one ahead, so
             // an update's only LDS round trip on the dependent chain is its state-plane read.
-            bool act = true, hitf = false;
             const uint32_t lim = a.update_cap > used ? a.update_cap - used : 0u;  // updates left
             uint4 q0 = erec[gbuf[lane]];
             uint4 q1 = erec[gbuf[64 + lane]];
@@ -1597,10 +1498,9 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
             else
                 chunk(std::false_type{});
             settle(~0u, (used == 1u && !a.first_tested) ? ~0u : 0u);  // the last update made
-            act = actm != 0u;
-            hitf = hitm != 0u;
+            const bool active = actm != 0u, hitf = hitm != 0u;
             capped = !hitf && used >= a.update_cap;
-            done = !act;
+            done = !active;
         } else
         for (uint32_t c = 0; c < ENV_CHUNK; ++c) {
             if (used >= a.update_cap) {
@@ -1673,10 +1573,10 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
         begin_steps(s);
     }
 #ifdef PBN_STAMPS
-    est[7] = __builtin_amdgcn_s_memrealtime();
-    for (uint32_t k = 0; k < 64; ++k) est[14] += (uint32_t)__shfl((int)ncapped, (int)k);
-    est[12] = blockIdx.x;
-    est[13] = __smid();
+    est[EST_END] = __builtin_amdgcn_s_memrealtime();
+    for (uint32_t k = 0; k < 64; ++k) est[EST_CAPPED] += (uint32_t)__shfl((int)ncapped, (int)k);
+    est[EST_BLOCK] = blockIdx.x;
+    est[EST_HW_ID] = __smid();
     const uint32_t wv = blockIdx.x * (ENV_BLOCK / 64) + threadIdx.x / 64;
     if (lane == 0 && wv < 16384)
         for (int k = 0; k < ENV_STAMPS; ++k) g_env_stamps[(uint64_t)wv * ENV_STAMPS + k] = est[k];
@@ -1686,15 +1586,17 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
 // ------------------------------------------------------------------ dispatch
 template <int KIND>
 static void* env_fn_w(int W, int replay, int fast, int grp) {
-    if (fast == 3) {
+    if (fast == ENV_MODE_GROUP) {
         if (KIND != KIND_PREDICTOR_MIX || replay) return nullptr;
         return env_grp_kernel(W, grp);
     }
     return by_words<8>(W, [=](auto w) {
-        if (fast == 2 && KIND == KIND_PREDICTOR_MIX && !replay) return (void*)k_env<w, KIND_PREDICTOR_MIX, 0, 2>;
-        if (fast == 4 && KIND == KIND_PREDICTOR_MIX && !replay) return (void*)k_env<w, KIND_PREDICTOR_MIX, 0, 4>;
-        if (fast) return replay ? (void*)k_env<w, KIND, 1, 1> : (void*)k_env<w, KIND, 0, 1>;
-        return replay ? (void*)k_env<w, KIND, 1, 0> : (void*)k_env<w, KIND, 0, 0>;
+        if (fast == ENV_MODE_COOP && KIND == KIND_PREDICTOR_MIX && !replay)
+            return (void*)k_env<w, KIND_PREDICTOR_MIX, 0, ENV_MODE_COOP>;
+        if (fast == ENV_MODE_TAIL && KIND == KIND_PREDICTOR_MIX && !replay)
+            return (void*)k_env<w, KIND_PREDICTOR_MIX, 0, ENV_MODE_TAIL>;
+        if (fast) return replay ? (void*)k_env<w, KIND, 1, ENV_MODE_COUNTERS> : (void*)k_env<w, KIND, 0, ENV_MODE_COUNTERS>;
+        return replay ? (void*)k_env<w, KIND, 1, ENV_MODE_CUBES> : (void*)k_env<w, KIND, 0, ENV_MODE_CUBES>;
     });
 }
 
@@ -1703,25 +1605,24 @@ static void* env_kernel(int W, int kind, int replay, int fast, int grp) {
                                       : env_fn_w<KIND_PROB_TABLE>(W, replay, fast, grp);
 }
 
-uint32_t env_lds_bytes(int W, uint32_t image_bytes, int fast, int grp, int n_nodes, uint32_t chunk) {
-    if (fast == 3) return image_bytes + 8u * (uint32_t)W * (BLOCK / (uint32_t)grp);  // one row per group
+uint32_t env_lds_bytes(int W, uint32_t image_bytes, int fast, int grp, uint32_t chunk) {
+    if (fast == ENV_MODE_GROUP) return image_bytes + 8u * (uint32_t)W * (BLOCK / (uint32_t)grp);  // one row per group
     const uint32_t planes = image_bytes + 8u * (uint32_t)W * ENV_BLOCK;
-    (void)n_nodes;
-    // fast == 4: 16 B of workgroup hand-off control after the per-wave draw buffers
-    return fast == 2 || fast == 4 ? planes + (ENV_BLOCK / 64) * env_gen_wave_bytes(chunk) + (fast == 4 ? 16u : 0u) : planes;
+    // ENV_MODE_TAIL: 16 B of workgroup hand-off control (WgCtl) after the per-wave draw buffers
+    const bool coop = fast == ENV_MODE_COOP || fast == ENV_MODE_TAIL;
+    return coop ? planes + (ENV_BLOCK / 64) * env_gen_wave_bytes(chunk) + (fast == ENV_MODE_TAIL ? 16u : 0u) : planes;
 }
 
 int launch_env_multi(int W, const EnvArgs& a, int replay, int grid, void* stream) {
     EnvArgs c = a;
     return launch(env_kernel(W, a.L.kind, replay, a.fast, a.grp), grid, env_block(a.fast),
-                  env_lds_bytes(W, a.L.bytes + a.erec_shift, replay ? std::min(a.fast, 1) : a.fast, a.grp, a.L.n_nodes,
-                                a.chunk),
+                  env_lds_bytes(W, a.L.bytes + a.erec_shift, replay ? std::min(a.fast, (int)ENV_MODE_COUNTERS) : a.fast, a.grp, a.chunk),
                   stream, &c);
 }
 
-int max_blocks_env(int W, int kind, int fast, int grp, uint32_t lds_bytes, int* blocks_per_cu, int n_nodes, uint32_t chunk) {
-    return occupancy(env_kernel(W, kind, 0, fast, grp), env_block(fast),
-                     env_lds_bytes(W, lds_bytes, fast, grp, n_nodes, chunk), blocks_per_cu);
+int max_blocks_env(int W, int kind, int fast, int grp, uint32_t lds_bytes, int* blocks_per_cu, uint32_t chunk) {
+    return occupancy(env_kernel(W, kind, 0, fast, grp), env_block(fast), env_lds_bytes(W, lds_bytes, fast, grp, chunk),
+                     blocks_per_cu);
 }
 
 #ifdef PBN_STAMPS

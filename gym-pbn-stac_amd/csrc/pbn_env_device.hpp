@@ -70,6 +70,11 @@ __device__ __forceinline__ bool attracting_plane(const P_t& P, const uint64_t* c
 
 __device__ __forceinline__ uint32_t has_zero_byte(uint32_t v) { return (v - 0x01010101u) & ~v & 0x80808080u; }
 
+// Predictor choice within one 16-B row of compact thresholds (Thr32): how many of the four the draw word reaches.
+__device__ __forceinline__ uint32_t cnt4(const uint4& t4, uint32_t a32) {
+    return (a32 >= t4.x ? 1u : 0u) + (a32 >= t4.y ? 1u : 0u) + (a32 >= t4.z ? 1u : 0u) + (a32 >= t4.w ? 1u : 0u);
+}
+
 // Inclusive prefix sum over the wave's 64 lanes (row_shr 1/2/4/8 inside each 16-lane row, then
 // row_bcast15 / row_bcast31 carry the row totals; lanes without a source add 0).
 // Inclusive max over the wave (the same DPP pattern; lanes without a source take 0): lane 63 holds the max.

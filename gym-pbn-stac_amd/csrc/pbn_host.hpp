@@ -61,7 +61,7 @@ struct pbn_envcfg {
     std::vector<uint64_t> reset;  // care [H_reset][W], then value [H_reset][W]
     int32_t horizon = 100, reward_success = 1000, action_cost = 1, first_tested = 0;
     std::mutex mu;                   // guards gen_image's construction
-    std::vector<uint8_t> gen_image;  // k_env modes 2/4: the LDS image as staged (env_gen_image), built once
+    std::vector<uint8_t> gen_image;  // k_env ENV_MODE_COOP / _TAIL: the LDS image as staged (env_gen_image), built once
                                      // (erec_shift is fixed by the network and the cubes)
     DevCache dev_image, dev_reset, dev_gen;
 };
@@ -150,10 +150,10 @@ struct Knobs {
     int env_grid_cap = 0;     // PBNSIM_ENV_GRID: the R6 kernel's workgroups (tests: lane refill, hand-offs), 0 = by size
     int env_tail = -1;        // PBNSIM_ENV_TAIL: the R6 kernel's tail-mode threshold (live envs per wave), -1 = default
     int env_lane_limit = 0;   // PBNSIM_ENV_LANES: lanes per wave taking envs in the tail-mode kernel, 0 = auto
-    bool env_steal = true;    // PBNSIM_ENV_STEAL=0: no hand-off of tail envs between a workgroup's waves (k_env, mode 4)
+    bool env_steal = true;    // PBNSIM_ENV_STEAL=0: no hand-off of tail envs between a workgroup's waves (k_env, ENV_MODE_TAIL)
     bool env_kernel_image = false;  // PBNSIM_ENV_KERNEL_IMAGE=1: k_env builds its LDS image (no host-built image)
     int env_helpers = 3;      // PBNSIM_ENV_HELPERS: at most this many tail helpers per session (0-3; 0 = off)
-    // PBNSIM_ENV_GRID_STEAL: grid-wide hand-off of tail envs (k_env, mode 4): 1 on, 0 off, unset = fused launches
+    // PBNSIM_ENV_GRID_STEAL: grid-wide hand-off of tail envs (k_env, ENV_MODE_TAIL): 1 on, 0 off, unset = fused launches
     // and update caps from GPOOL_MIN_CAP (below it one env step's loops are too short to repay the waiting
     // workgroups' residency)
     int env_grid_steal = -1;
@@ -170,10 +170,10 @@ struct Knobs {
 
 // What env_plan (pbn_abi_env.cpp) decides for one R6 launch; the batch keeps the last launched one.
 struct EnvPlan {
-    int mode = -1;            // EnvArgs::fast: 0 cube matching, 1 byte counters, 2 cooperative draws, 3 group mode, 4 tail kernel
+    int mode = -1;            // EnvArgs::fast, an EnvMode (pbn_params.hpp)
     int grp = 0;              // lanes per env
-    uint32_t erec_shift = 0;  // LDS bytes the 16-B env records add (modes 2 / 4)
-    uint32_t chunk = 0;       // draw-round chunk (modes 2 / 4)
+    uint32_t erec_shift = 0;  // LDS bytes the 16-B env records add (ENV_MODE_COOP / _TAIL)
+    uint32_t chunk = 0;       // draw-round chunk (ENV_MODE_COOP / _TAIL)
     int bpc = 1;              // resident workgroups per CU
     uint32_t lane_limit = 0, tail_max = 0;
     int grid = 0;             // workgroups

@@ -16,6 +16,14 @@ enum {
     STREAM_SYNC_PERT = 8
 };
 enum { STORE_FULL = 0, STORE_DIRTY = 1 };
+// R6 env-step modes: EnvArgs::fast, EnvPlan::mode and k_env's template parameter
+enum EnvMode {
+    ENV_MODE_CUBES = 0,     // the state matched against every cube after a change
+    ENV_MODE_COUNTERS = 1,  // <= 8 cubes, each caring about <= 255 nodes: packed byte counters
+    ENV_MODE_COOP = 2,      // and predictor mix, <= 16 predictors per node, Philox: cooperative draws
+    ENV_MODE_GROUP = 3,     // group mode (k_env_grp)
+    ENV_MODE_TAIL = 4       // as ENV_MODE_COOP with <= 4 cubes (one counter word): the tail kernel
+};
 
 constexpr int BLOCK = 256;          // 4 wave64 per workgroup
 #ifndef PBN_ENV_BLOCK
@@ -150,12 +158,9 @@ struct EnvArgs {
     uint32_t off_ndelta;     // per node: uint2 packed mismatch-counter deltas (fast attractor test)
     unsigned long long* counter;  // work-queue head (zeroed per launch)
     int32_t n_cubes;
-    int32_t fast;            // 1: <= 8 cubes, each caring about <= 255 nodes (byte counters);
-                             // 2: and predictor mix with <= 16 predictors per node, Philox: the
-                             //    draws are generated cooperatively by the whole wave;
-                             // 3: group mode (k_env_grp); 4: as 2 with <= 4 cubes (one counter word)
-    uint32_t off_gen;        // fast == 2 / 4: per-wave draw buffers (ENV_GEN_WAVE_BYTES each);
-                             // fast == 3: per-group env rows (2W dwords per group of grp lanes)
+    int32_t fast;            // the kernel's mode: an EnvMode (above)
+    uint32_t off_gen;        // ENV_MODE_COOP / _TAIL: per-wave draw buffers (ENV_GEN_WAVE_BYTES each);
+                             // ENV_MODE_GROUP: per-group env rows (2W dwords per group of grp lanes)
     uint64_t B, env_base, seed;
     uint32_t call_idx, update_cap;
     int32_t A, offset, dedup, horizon, reward_success, action_cost;
@@ -163,24 +168,24 @@ struct EnvArgs {
     const int64_t* draw_off;  // replay mode: [B+1]
     const uint32_t* draws_i;
     const uint64_t* draws_k;
-    int32_t grp;              // fast == 3: lanes per env (2, 4 or 8), k_env_grp
+    int32_t grp;              // ENV_MODE_GROUP: lanes per env (2, 4 or 8), k_env_grp
     uint32_t n_calls;         // env steps per env in this launch: actions [n_calls][B][A], outputs
                               // [n_calls][B]...; step t draws with Philox c1 = call_idx + t
-    uint32_t erec_shift;      // fast == 2: LDS bytes the 16-B env records add over the 8-B records
+    uint32_t erec_shift;      // ENV_MODE_COOP / _TAIL: LDS bytes the 16-B env records add over the 8-B records
                               // (off_cubes / off_target / off_ndelta / off_gen are LDS offsets)
-    uint32_t tail_max;        // fast == 4: a wave whose queue ran dry resolves its envs one at a time,
+    uint32_t tail_max;        // ENV_MODE_TAIL: a wave whose queue ran dry resolves its envs one at a time,
                               // 64 updates per block, once it holds at most this many (0 = never)
-    uint32_t lane_limit;      // fast == 4: lanes per wave that take envs from the work queue (64 = all;
+    uint32_t lane_limit;      // ENV_MODE_TAIL: lanes per wave that take envs from the work queue (64 = all;
                               // <= tail_max: every wave in tail mode from its first env)
-    int32_t steal_local;      // fast == 4: hand-off of tail envs between the waves of a workgroup (LDS)
+    int32_t steal_local;      // ENV_MODE_TAIL: hand-off of tail envs between the waves of a workgroup (LDS)
     uint32_t* steal_count;    // envs handed off in this launch (diagnostics), zeroed per launch
-    const void* gen_img;      // fast == 2 / 4: the LDS image as staged (host-built, pbn_image.cpp env_gen_image);
+    const void* gen_img;      // ENV_MODE_COOP / _TAIL: the LDS image as staged (host-built, pbn_image.cpp env_gen_image);
                               // null: the kernel builds it from img
-    uint32_t chunk;           // fast == 2 / 4: updates per lane between draw rounds (ENV_CHUNK_SMALL / _LARGE)
-    int32_t tail_helpers;     // fast == 4 (with steal_local): up to this many (<= 3) idle waves of the workgroup prepare a long tail
+    uint32_t chunk;           // ENV_MODE_COOP / _TAIL: updates per lane between draw rounds (ENV_CHUNK_SMALL / _LARGE)
+    int32_t tail_helpers;     // ENV_MODE_TAIL (with steal_local): up to this many (<= 3) idle waves of the workgroup prepare a long tail
                               // session's blocks ahead (draws, records, writer masks) into the session wave's
                               // LDS ring, so the session wave only resolves (k_env, tail helpers)
-    // fast == 4 (with steal_local): grid-wide hand-off of tail envs to workgroups that have run out of work
+    // ENV_MODE_TAIL (with steal_local): grid-wide hand-off of tail envs to workgroups that have run out of work
     // (k_env, "grid pool"). Device memory, control words zeroed per launch:
     uint32_t* gpool_ctl;      // [0] slots reserved by pushers, [1] tickets taken by idle workgroups, [2] live:
                               // workgroups working + envs in the pool, [3] envs pushed, [4] waits given up,
@@ -364,7 +369,7 @@ constexpr uint32_t ENV_TAIL_DEFAULT = 16;
 // slot; e.g. 8,192 envs, cap 4,096: 0.19 vs 0.96 ms per step); at 32,768 the spec attractors' per-step
 // line is 31 % slower (short env steps queue behind long ones in one wave), so 6 per slot
 constexpr uint64_t ENV_ONE_LANE_ENVS_PER_SLOT = 6;
-// Cooperative-draw kernels (EnvArgs::fast 2 / 4) take their chunk (updates per lane between draw
+// Cooperative-draw kernels (ENV_MODE_COOP / _TAIL) take their chunk (updates per lane between draw
 // rounds) per launch, EnvArgs::chunk: 48 by default -- fewer chunk prologues on the long per-lane
 // chains of a per-step launch (131,072 envs, cap 4,096: 1.22 -> 1.17 ms per step) -- and 32 where the
 // smaller draw buffers let one more workgroup onto a CU and the launch is throughput-bound (a fused
@@ -374,10 +379,9 @@ constexpr uint32_t ENV_CHUNK_SMALL = 32, ENV_CHUNK_LARGE = 48;
 // a wave's draw buffer: the draw table [chunk][64] u16, 64 B (the hand-off flag in tail mode), the
 // shared rounds' counter table [64] uint4 by rank (the hand-off box in tail mode)
 constexpr uint32_t env_gen_wave_bytes(uint32_t chunk) { return chunk * 64u * 2u + 64u + 64u * 16u; }
-int max_blocks_env(int W, int kind, int fast, int grp, uint32_t lds_bytes, int* blocks_per_cu, int n_nodes = 0,
-                   uint32_t chunk = ENV_CHUNK_LARGE);
-uint32_t env_lds_bytes(int W, uint32_t image_bytes, int fast, int grp, int n_nodes = 0, uint32_t chunk = ENV_CHUNK_LARGE);
-inline int env_block(int fast) { return fast == 3 ? BLOCK : ENV_BLOCK; }  // threads per workgroup of the R6 kernel
+int max_blocks_env(int W, int kind, int fast, int grp, uint32_t lds_bytes, int* blocks_per_cu, uint32_t chunk = ENV_CHUNK_LARGE);
+uint32_t env_lds_bytes(int W, uint32_t image_bytes, int fast, int grp, uint32_t chunk = ENV_CHUNK_LARGE);
+inline int env_block(int fast) { return fast == ENV_MODE_GROUP ? BLOCK : ENV_BLOCK; }  // threads per workgroup of the R6 kernel
 int launch_mt_seed(int W, const MTArgs& a, int grid, void* stream);
 int launch_mt_step(int W, const MTArgs& a, int n_cu, void* stream);  // grid from the kernel's occupancy
 uint32_t ssd_block(const SSDArgs& a);
