@@ -4,15 +4,26 @@
 // launch-bound on the host.
 #include "pbn_host.hpp"
 
-static int step_launch(pbn_batch* b, uint32_t T, uint64_t update_base, int replay, const void* d_i, const void* d_k,
-                       const uint64_t* ubase_dev = nullptr, bool timed = true) {
+// The envs one step launch covers and the stream it goes to: the whole batch on the batch's stream, or one
+// launch chain's slice (pbn_batch::Chains) on a stream of the caller's choice.
+struct StepRange {
+    uint64_t off, len;
+    hipStream_t stream;
+};
+static StepRange whole_batch(const pbn_batch* b) { return {0, b->B, b->stream}; }
+static StepRange chain_range(const pbn_batch* b, int c, hipStream_t stream) {
+    return {b->ch.sl[c].off, b->ch.sl[c].len, stream};
+}
+
+static int step_launch(pbn_batch* b, const StepRange& r, uint32_t T, uint64_t update_base, int replay, const void* d_i,
+                       const void* d_k, const uint64_t* ubase_dev = nullptr, bool timed = true) {
     StepArgs a{};
     a.ubase_dev = ubase_dev;
-    a.state = b->d_state;
+    a.state = b->d_state + r.off * (uint64_t)b->W;
     a.img = b->d_image;
     a.L = b->net->L;
-    a.B = b->B;
-    a.env_base = b->env_base;
+    a.B = r.len;
+    a.env_base = b->env_base + r.off;
     a.seed = b->seed;
     a.update_base = update_base;
     a.T = T;
@@ -28,12 +39,12 @@ static int step_launch(pbn_batch* b, uint32_t T, uint64_t update_base, int repla
     const bool rollout = T > 1 && !replay;  // k_rollout (or k_rollout_grp), 256-thread groups
     a.grp = rollout ? b->roll_group : 1;
     const uint64_t K = rollout ? 1u : (uint64_t)b->knob.envs_per_thread;
-    const uint64_t lanes = rollout ? b->B * (uint64_t)a.grp : (b->B + K - 1) / K;
+    const uint64_t lanes = rollout ? r.len * (uint64_t)a.grp : (r.len + K - 1) / K;
     const int sb = (replay || rollout) ? BLOCK : b->step_block;
     const int grid = replay    ? b->grid_for(lanes, b->bpc_base)
                      : rollout ? b->grid_for(lanes, b->bpc_roll, sb)
                                : b->grid_for(lanes, b->bpc_step, sb);
-    int e = launch_step(b->W, a, store, replay, sb, grid, b->stream);
+    int e = launch_step(b->W, a, store, replay, sb, grid, r.stream);
     if (e) return fail(PBN_E_HIP, "k_step launch: %s", hipGetErrorString((hipError_t)e));
     return timed ? b->ev_end(stop) : 0;
 }
@@ -49,23 +60,29 @@ static bool step_graph_ready(pbn_batch* b) {
     if (b->sg.broken || b->sg.off || !b->stream) return false;  // the null stream cannot capture
     if (b->sg.ubase.ensure(64)) return false;
     bool ok = true;
-    for (int j = 0; ok && j < STEP_GRAPH_SIZES; ++j) {
-        const uint32_t K = STEP_GRAPH_K >> j;
-        hipGraph_t g = nullptr;
-        ok = hipStreamBeginCapture(b->stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
-        bool launched = ok;
-        for (uint32_t k = 0; launched && k < K; ++k)
-            launched = step_launch(b, 1, k, 0, nullptr, nullptr, (const uint64_t*)b->sg.ubase.p, false) == 0;
-        if (launched) launched = launch_bump((uint64_t*)b->sg.ubase.p, K, b->stream) == 0;
-        if (ok) ok = hipStreamEndCapture(b->stream, &g) == hipSuccess && launched && g;
-        if (ok) ok = hipGraphInstantiate(&b->sg.graph[j], g, nullptr, nullptr, 0) == hipSuccess;
-        if (g) (void)hipGraphDestroy(g);
-    }
-    if (!ok) {
-        for (hipGraphExec_t& g : b->sg.graph) {
-            if (g) (void)hipGraphExecDestroy(g);
-            g = nullptr;
+    // every chain's graphs are captured on the batch's stream (a captured launch keeps no stream); chain c's
+    // read and bump its own counter, so one chain's k_bump never races another chain's reads
+    for (int c = 0; ok && c < b->ch.n; ++c)
+        for (int j = 0; ok && j < STEP_GRAPH_SIZES; ++j) {
+            const uint32_t K = STEP_GRAPH_K >> j;
+            uint64_t* counter = (uint64_t*)b->sg.ubase.p + c;
+            const StepRange r = chain_range(b, c, b->stream);
+            hipGraph_t g = nullptr;
+            ok = hipStreamBeginCapture(b->stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
+            bool launched = ok;
+            for (uint32_t k = 0; launched && k < K; ++k)
+                launched = step_launch(b, r, 1, k, 0, nullptr, nullptr, counter, false) == 0;
+            if (launched) launched = launch_bump(counter, K, b->stream) == 0;
+            if (ok) ok = hipStreamEndCapture(b->stream, &g) == hipSuccess && launched && g;
+            if (ok) ok = hipGraphInstantiate(&b->sg.graph[c][j], g, nullptr, nullptr, 0) == hipSuccess;
+            if (g) (void)hipGraphDestroy(g);
         }
+    if (!ok) {
+        for (auto& chain : b->sg.graph)
+            for (hipGraphExec_t& g : chain) {
+                if (g) (void)hipGraphExecDestroy(g);
+                g = nullptr;
+            }
         b->sg.broken = true;
         (void)hipGetLastError();  // the failed capture is not the caller's error
         g_err.clear();
@@ -84,19 +101,30 @@ static int exact_graph_build(pbn_batch* b, uint32_t n) {
     // capture and instantiate into a fresh exec first: a failed capture leaves the cached graphs
     // as they were and marks the batch, so later calls do not re-capture n launches to fail again
     // no k_bump: pbn_step writes the device counter before every replay of an exact graph
-    hipGraph_t g = nullptr;
-    hipGraphExec_t x = nullptr;
-    bool ok = hipStreamBeginCapture(b->stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
-    bool launched = ok;
-    for (uint32_t k = 0; launched && k < n; ++k)
-        launched = step_launch(b, 1, k, 0, nullptr, nullptr, (const uint64_t*)b->sg.ubase.p, false) == 0;
-    if (ok) ok = hipStreamEndCapture(b->stream, &g) == hipSuccess && launched && g;
-    if (ok) ok = hipGraphInstantiate(&x, g, nullptr, nullptr, 0) == hipSuccess;
-    // upload now, so the first replay (e.g. a timed one) does not pay for it
-    if (ok) ok = hipGraphUpload(x, b->stream) == hipSuccess;
-    if (g) (void)hipGraphDestroy(g);
+    // one graph per launch chain (each a linear run over that chain's envs), captured on the batch's stream
+    hipGraphExec_t x[STEP_CHAINS_MAX] = {};
+    bool ok = true;
+    for (int c = 0; ok && c < b->ch.n; ++c) {
+        const StepRange r = chain_range(b, c, b->stream);
+        hipGraph_t g = nullptr;
+        ok = hipStreamBeginCapture(b->stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
+        bool launched = ok;
+        for (uint32_t k = 0; launched && k < n; ++k)
+            launched = step_launch(b, r, 1, k, 0, nullptr, nullptr, (const uint64_t*)b->sg.ubase.p + c, false) == 0;
+        if (ok) ok = hipStreamEndCapture(b->stream, &g) == hipSuccess && launched && g;
+        if (ok) ok = hipGraphInstantiate(&x[c], g, nullptr, nullptr, 0) == hipSuccess;
+        // upload now, on the stream that will replay it, so the first replay (e.g. a timed one) does not pay for it
+        if (ok) ok = hipGraphUpload(x[c], b->chain_stream(c)) == hipSuccess;
+        if (g) (void)hipGraphDestroy(g);
+    }
+    // the extra chains' uploads are done before anything below may destroy an exec (setup, not a replay loop)
+    for (int c = 1; c < b->ch.n; ++c) (void)hipStreamSynchronize(b->ch.stream[c]);
+    auto drop = [&] {
+        for (hipGraphExec_t& e : x)
+            if (e) (void)hipGraphExecDestroy(e);
+    };
     if (!ok) {
-        if (x) (void)hipGraphExecDestroy(x);
+        drop();
         b->sg.exact_broken = true;
         (void)hipGetLastError();
         g_err.clear();
@@ -105,18 +133,19 @@ static int exact_graph_build(pbn_batch* b, uint32_t n) {
     int slot = 0;
     for (int j = 1; j < pbn_batch::StepGraphs::EXACT_GRAPHS; ++j)
         if (b->sg.exact_used[j] < b->sg.exact_used[slot]) slot = j;
-    if (b->sg.exact_graph[slot]) {
-        // the evicted exec may still be queued or running from an earlier asynchronous pbn_step on
-        // this stream (HIP documents no deferred free): drain the stream first. Eviction happens
-        // only at capture time, never in a steady replay loop.
+    if (b->sg.exact_graph[slot][0]) {
+        // the evicted execs may still be queued or running from an earlier asynchronous pbn_step
+        // (HIP documents no deferred free): drain the stream first -- every call joined its chains
+        // into it. Eviction happens only at capture time, never in a steady replay loop.
         if (hipStreamSynchronize(b->stream) != hipSuccess) {
-            (void)hipGraphExecDestroy(x);
+            drop();
             (void)fail(PBN_E_HIP, "stream sync before graph eviction failed");
             return -1;
         }
-        (void)hipGraphExecDestroy(b->sg.exact_graph[slot]);
+        for (hipGraphExec_t& e : b->sg.exact_graph[slot])
+            if (e) (void)hipGraphExecDestroy(e);
     }
-    b->sg.exact_graph[slot] = x;
+    for (int c = 0; c < STEP_CHAINS_MAX; ++c) b->sg.exact_graph[slot][c] = x[c];
     b->sg.exact_n[slot] = n;
     b->sg.exact_used[slot] = ++b->sg.exact_clock;
     return slot;
@@ -124,7 +153,7 @@ static int exact_graph_build(pbn_batch* b, uint32_t n) {
 
 static int exact_graph_find(pbn_batch* b, uint32_t n) {
     for (int j = 0; j < pbn_batch::StepGraphs::EXACT_GRAPHS; ++j)
-        if (b->sg.exact_graph[j] && b->sg.exact_n[j] == n) return j;
+        if (b->sg.exact_graph[j][0] && b->sg.exact_n[j] == n) return j;
     return -1;
 }
 
@@ -134,11 +163,26 @@ static bool stream_capturing(pbn_batch* b) {
     return cap != hipStreamCaptureStatusNone;
 }
 
-// device counter <- update_count (two 32-bit memsets: stream-ordered, no host buffer)
+// every chain's device counter <- update_count (one tiny kernel on the batch's stream, ahead of the fork)
 static int upload_update_count(pbn_batch* b) {
-    uint32_t* c = (uint32_t*)b->sg.ubase.p;
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)c, (int)(uint32_t)b->update_count, 1, b->stream));
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(c + 1), (int)(uint32_t)(b->update_count >> 32), 1, b->stream));
+    if (int e = launch_set_counters((uint64_t*)b->sg.ubase.p, b->update_count, (uint32_t)b->ch.n, b->stream))
+        return fail(PBN_E_HIP, "k_set_counters launch: %s", hipGetErrorString((hipError_t)e));
+    return 0;
+}
+
+// A chained call's fork: the extra chains' streams wait for everything queued on the batch's stream so far.
+static int chains_fork(pbn_batch* b) {
+    HIP_TRY(hipEventRecord(b->ch.fork, b->stream));
+    for (int c = 1; c < b->ch.n; ++c) HIP_TRY(hipStreamWaitEvent(b->ch.stream[c], b->ch.fork, 0));
+    return 0;
+}
+
+// ... and its join: whatever is queued on the batch's stream next waits for every chain's launches.
+static int chains_join(pbn_batch* b) {
+    for (int c = 1; c < b->ch.n; ++c) {
+        HIP_TRY(hipEventRecord(b->ch.done[c], b->ch.stream[c]));
+        HIP_TRY(hipStreamWaitEvent(b->stream, b->ch.done[c], 0));
+    }
     return 0;
 }
 
@@ -162,6 +206,7 @@ int pbn_step_prepare(pbn_batch* b, uint32_t n_updates) {
         return fail(PBN_E_INVALID, "n_updates=%u above PBN_STEP_PREPARE_MAX", n_updates);
     SET_DEV(b);
     if (n_updates < 2 || b->sg.off || stream_capturing(b)) return 0;
+    if (b->ch.n > 1 && n_updates < b->ch.min_updates) return 0;  // an unsplit call of a batch with chains: plain launches
     // on failure pbn_step falls back to plain launches; runs longer than STEP_GRAPH_K replay the
     // power-of-two graphs (one graph of thousands of launches replayed slower: 3.43 vs 3.16 us per
     // launch at 65,536 Bittner-28 envs)
@@ -177,52 +222,89 @@ int pbn_step(pbn_batch* b, uint32_t n_updates) {
     // not while the caller is capturing the stream into a graph of its own: plain launches then
     const bool cap = stream_capturing(b);
     const uint32_t smallest = STEP_GRAPH_K >> (STEP_GRAPH_SIZES - 1);
+    // a run: two or more updates, no event pair per launch, not inside the caller's capture. Only a run
+    // replays graphs, and only a run is split into the batch's launch chains.
+    const bool run = !cap && b->tm.mode != 1 && n_updates >= 2;
+    const bool chained = run && b->ch.n > 1 && n_updates >= b->ch.min_updates;
+    const int S = chained ? b->ch.n : 1;
+    // the graphs of a batch with chains cover the chains' slices: its unsplit calls launch plainly
+    const bool graphs = run && !b->sg.off && (b->ch.n == 1 || chained);
     int exact = -1;
-    if (!cap && b->tm.mode != 1 && n_updates >= 2 && !b->sg.off) {
+    if (graphs) {
         exact = exact_graph_find(b, n_updates);
         // a length seen twice in a row gets its own graph (an RL loop's fixed step count)
         if (exact < 0 && n_updates == b->sg.last_n && n_updates <= STEP_GRAPH_K)
             exact = exact_graph_build(b, n_updates);
     }
     b->sg.last_n = n_updates;
-    if (exact >= 0) {
+    const bool pow2 = exact < 0 && graphs && n_updates >= smallest && step_graph_ready(b);
+    if (exact >= 0 || pow2)
         if (int rc = upload_update_count(b)) return rc;
-        hipEvent_t stop;
-        if (int rc = b->ev_begin(&stop)) return rc;
-        if (b->tm.mode == 2) b->tm.region_launches += n_updates - 1;  // ev_begin counted one
-        HIP_TRY(hipGraphLaunch(b->sg.exact_graph[exact], b->stream));
-        if (int rc = b->ev_end(stop)) return rc;
-        b->sg.exact_used[exact] = ++b->sg.exact_clock;
-        b->update_count += n_updates;
-        return 0;
+    if (chained) {
+        // the call counts as n_updates launches (one per step, not per chain); the region's start, like its
+        // stop, is recorded on the batch's stream: ahead of the fork, behind the join
+        if (b->tm.mode == 2) {
+            hipEvent_t stop;
+            if (int rc = b->ev_begin(&stop)) return rc;
+            b->tm.region_launches += n_updates - 1;  // ev_begin counted one
+        }
+        if (int rc = chains_fork(b)) return rc;
     }
-    if (n_updates >= smallest && b->tm.mode != 1 && !cap && step_graph_ready(b)) {
-        if (int rc = upload_update_count(b)) return rc;
-        for (int j = 0; j < STEP_GRAPH_SIZES; ++j) {
-            const uint32_t K = STEP_GRAPH_K >> j;
-            while (n_updates - t >= K && (j == 0 || n_updates - t < 2 * K)) {
-                hipEvent_t stop;
-                if (int rc = b->ev_begin(&stop)) return rc;
-                if (b->tm.mode == 2) b->tm.region_launches += K - 1;  // ev_begin counted one
-                HIP_TRY(hipGraphLaunch(b->sg.graph[j], b->stream));
-                if (int rc = b->ev_end(stop)) return rc;
-                b->update_count += K;
-                t += K;
+    // k updates about to be queued as one graph replay (per chain)
+    auto count = [&](uint32_t k) -> int {
+        if (chained) return 0;
+        hipEvent_t stop;  // stays null: no graph replays in timing mode 1
+        if (int rc = b->ev_begin(&stop)) return rc;
+        if (b->tm.mode == 2) b->tm.region_launches += k - 1;  // ev_begin counted one
+        return 0;
+    };
+    // the host alternates chains replay by replay and launch by launch: each chain's stream holds its own
+    // launches in update order
+    auto queue = [&]() -> int {
+        if (exact >= 0) {
+            if (int rc = count(n_updates)) return rc;
+            for (int c = 0; c < S; ++c) HIP_TRY(hipGraphLaunch(b->sg.exact_graph[exact][c], b->chain_stream(c)));
+            b->sg.exact_used[exact] = ++b->sg.exact_clock;
+            b->update_count += n_updates;
+            return 0;
+        }
+        if (pow2) {
+            for (int j = 0; j < STEP_GRAPH_SIZES; ++j) {
+                const uint32_t K = STEP_GRAPH_K >> j;
+                while (n_updates - t >= K && (j == 0 || n_updates - t < 2 * K)) {
+                    if (int rc = count(K)) return rc;
+                    for (int c = 0; c < S; ++c) HIP_TRY(hipGraphLaunch(b->sg.graph[c][j], b->chain_stream(c)));
+                    b->update_count += K;
+                    t += K;
+                }
             }
         }
+        for (; t < n_updates; t++) {
+            if (!chained) {
+                if (int rc = step_launch(b, whole_batch(b), 1, b->update_count, 0, nullptr, nullptr)) return rc;
+            } else {
+                for (int c = 0; c < S; ++c)
+                    if (int rc = step_launch(b, chain_range(b, c, b->chain_stream(c)), 1, b->update_count, 0, nullptr,
+                                             nullptr, nullptr, false))
+                        return rc;
+            }
+            b->update_count++;
+        }
+        return 0;
+    };
+    int rc = queue();
+    if (chained) {  // also after a failed launch: what was queued on the chains stays ordered
+        const int jrc = chains_join(b);
+        if (!rc) rc = jrc;
     }
-    for (; t < n_updates; t++) {
-        if (int rc = step_launch(b, 1, b->update_count, 0, nullptr, nullptr)) return rc;
-        b->update_count++;
-    }
-    return 0;
+    return rc;
 }
 
 int pbn_rollout(pbn_batch* b, uint32_t n_updates) {
     CHECK_NN(b, "batch");
     if (!n_updates) return 0;
     SET_DEV(b);
-    if (int rc = step_launch(b, n_updates, b->update_count, 0, nullptr, nullptr)) return rc;
+    if (int rc = step_launch(b, whole_batch(b), n_updates, b->update_count, 0, nullptr, nullptr)) return rc;
     b->update_count += n_updates;
     return 0;
 }
@@ -239,7 +321,7 @@ int pbn_step_replay(pbn_batch* b, const uint32_t* node_idx, const uint64_t* k53,
     if (int rc = b->s_replay_k.ensure(8 * n)) return rc;
     HIP_TRY(hipMemcpyAsync(b->s_replay_i.p, node_idx, 4 * n, hipMemcpyHostToDevice, b->stream));
     HIP_TRY(hipMemcpyAsync(b->s_replay_k.p, k53, 8 * n, hipMemcpyHostToDevice, b->stream));
-    if (int rc = step_launch(b, n_updates, 0, 1, b->s_replay_i.p, b->s_replay_k.p)) return rc;
+    if (int rc = step_launch(b, whole_batch(b), n_updates, 0, 1, b->s_replay_i.p, b->s_replay_k.p)) return rc;
     HIP_TRY(hipStreamSynchronize(b->stream));
     return 0;
 }
@@ -255,7 +337,7 @@ int pbn_step_forced(pbn_batch* b, const uint32_t* node_idx, uint32_t n_updates) 
     HIP_TRY(hipMemcpyAsync(b->s_replay_i.p, node_idx, 4 * n, hipMemcpyHostToDevice, b->stream));
     // replay-mode kernel with no k53 array: update t takes the choice word of Philox step update
     // update_count + t (the draw pbn_step would use), so the stream stays in step with pbn_step
-    if (int rc = step_launch(b, n_updates, b->update_count, 1, b->s_replay_i.p, nullptr)) return rc;
+    if (int rc = step_launch(b, whole_batch(b), n_updates, b->update_count, 1, b->s_replay_i.p, nullptr)) return rc;
     b->update_count += n_updates;
     HIP_TRY(hipStreamSynchronize(b->stream));  // the staging buffer is reused by the next call
     return 0;

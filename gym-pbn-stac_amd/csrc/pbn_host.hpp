@@ -17,6 +17,7 @@
 #endif
 
 #include "../../include/pbn_abi.h"
+#include "pbn_chain_split.hpp"
 #include "pbn_params.hpp"
 
 using namespace pbn;
@@ -135,6 +136,14 @@ inline int check_action_shape(int A, int offset) {
 constexpr uint32_t STEP_GRAPH_K = 64;  // longest captured run of step launches
 constexpr int STEP_GRAPH_SIZES = 6;     // graphs of 64, 32, 16, 8, 4 and 2 launches
 constexpr uint64_t STEP_GRAPH_MAX_WORDS = 1ull << 20;  // state words from which step mode launches plainly
+// ... and from which a batch stepped as two or more launch chains does: each step is one launch per chain, and
+// the host issues plain launches at 3.3-4.4 us each (1M Bittner-200 envs, two chains: 8.5 us per step plain,
+// 5.45 as graphs; 2M: 11.6 vs 10.5; 4M: 19.8 vs 20.5)
+constexpr uint64_t STEP_CHAIN_GRAPH_MAX_WORDS = 1ull << 24;
+// Updates from which a call is split into the chains chosen by size: the fork, the join and a graph start per
+// chain cost a call about 20 us (1M Bittner-200 envs, bench.py --warmup 5, us per step, one chain -> two:
+// 20 steps 9.7 -> 10.6, 64 steps 8.8 -> 8.7, 200 steps 8.0 -> 7.5; 1,000 steps after 200: 6.5 -> 5.9)
+constexpr uint32_t STEP_CHAIN_MIN_UPDATES = 128;
 
 // Launch knobs read from PBNSIM_* once at pbn_batch_create (read_knobs, pbn_abi.cpp): measurement / tests.
 struct Knobs {
@@ -142,6 +151,7 @@ struct Knobs {
     int envs_per_thread = 2;       // PBNSIM_ENVS_PER_THREAD: K, envs each thread walks per launch (pipelined)
     int step_block = 0;            // PBNSIM_STEP_BLOCK: 256 / 1024 threads per workgroup of the step kernel, 0 = by size
     int step_graph = -1;           // PBNSIM_STEP_GRAPH=0/1 forces step mode without / with HIP graphs, -1 = by size
+    int step_chains = 0;           // PBNSIM_STEP_CHAINS: 1 / 2 / 4 launch chains of pbn_step, 0 = by size
     int roll_group = -1;           // PBNSIM_ROLL_GROUP: lanes per env of the rollout kernel, -1 = by size
     bool env_no_gen = false;  // PBNSIM_ENV_NO_GEN: no cooperative draw generation
     int env_group = 0;        // PBNSIM_ENV_GROUP: lanes per env (1 = lane mode), 0 = by batch size
@@ -208,9 +218,10 @@ struct pbn_batch {
         // device costs more than host submission, which a long kernel hides: 1M Bittner-200 envs, 20
         // launches: 9.3 us per launch plain vs 9.9 us as one replay); PBNSIM_STEP_GRAPH=0/1 forces it
         bool off = false;
-        // graph[j]: (STEP_GRAPH_K >> j) step launches + k_bump, captured once (all sizes at the
-        // first call of two or more steps)
-        hipGraphExec_t graph[STEP_GRAPH_SIZES] = {};
+        // graph[c][j]: (STEP_GRAPH_K >> j) step launches of chain c's envs + k_bump on chain c's counter,
+        // captured once (all sizes and chains at the first call of two or more steps). A graph holds one
+        // chain only: it is a linear run of kernels.
+        hipGraphExec_t graph[STEP_CHAINS_MAX][STEP_GRAPH_SIZES] = {};
         bool built = false;
         bool broken = false;        // capture or instantiation failed once: plain launches
         bool exact_broken = false;  // an exact-length capture failed once: no more of them
@@ -218,12 +229,24 @@ struct pbn_batch {
         // call with the same n); each extra replay in a call costs a graph start on the device (~13 us)
         static constexpr int EXACT_GRAPHS = 4;
         uint32_t exact_n[EXACT_GRAPHS] = {};
-        hipGraphExec_t exact_graph[EXACT_GRAPHS] = {};
+        hipGraphExec_t exact_graph[EXACT_GRAPHS][STEP_CHAINS_MAX] = {};  // [slot][chain]
         uint64_t exact_used[EXACT_GRAPHS] = {};  // LRU stamps
         uint64_t exact_clock = 0;
         uint32_t last_n = 0;
-        DevBuf ubase;  // device copy of update_count for graph replays
+        DevBuf ubase;  // device copies of update_count for graph replays, one 8-byte counter per chain
     } sg;
+    // Launch chains of step mode (pbn_step): chain c steps the envs of sl[c] on its own stream, chain 0 on
+    // `stream`. A call forks the extra streams off `stream` and joins them back into it, so everything else
+    // queued on `stream` keeps its order against the whole batch.
+    struct Chains {
+        int n = 1;                                   // chains in use (pbn_batch_info.step_chains)
+        uint32_t min_updates = 2;                    // calls of fewer updates run as one chain (2 = every run)
+        ChainSlice sl[STEP_CHAINS_MAX];              // sl[0 .. n): the batch in order
+        hipStream_t stream[STEP_CHAINS_MAX] = {};    // [1 .. n): the batch's own, non-blocking; [0] unused
+        hipEvent_t done[STEP_CHAINS_MAX] = {};       // [1 .. n): end of chain c's launches of a call
+        hipEvent_t fork = nullptr;
+    } ch;
+    hipStream_t chain_stream(int c) const { return c ? ch.stream[c] : stream; }
     struct R6 {
         uint32_t calls = 0;        // env steps launched (Philox call index)
         DevBuf counter;            // env-step work-queue head

@@ -343,6 +343,7 @@ struct ReachArgs {
 enum { REACH_K_UNSTABLE = 0, REACH_K_SEED, REACH_K_EXPAND, REACH_K_BACK_START, REACH_K_BACK, REACH_K_HULL };
 int launch_reach(int W, int which, const ReachArgs& a, int grid, void* stream);
 int launch_bump(uint64_t* p, uint64_t k, void* stream);
+int launch_set_counters(uint64_t* p, uint64_t v, uint32_t n, void* stream);
 int launch_step(int W, const StepArgs& a, int store_mode, int replay, int sb, int grid, void* stream);
 uint32_t step_lds_bytes(int W, uint32_t image_bytes, int sb, int grp = 1);
 int launch_init(int W, const InitArgs& a, int grid, void* stream);

@@ -515,4 +515,16 @@ int launch_bump(uint64_t* p, uint64_t k, void* stream) {
     return (int)hipLaunchKernel((const void*)k_bump, dim3(1), dim3(64), kargs, 0, (hipStream_t)stream);
 }
 
+// Sets the device-side update counters p[0 .. n) (one per launch chain, n <= 64) to v in front of a call's
+// graph replays.
+__global__ void k_set_counters(uint64_t* p, uint64_t v, uint32_t n) {
+    if (threadIdx.x < n) p[threadIdx.x] = v;
+}
+
+int launch_set_counters(uint64_t* p, uint64_t v, uint32_t n, void* stream) {
+    if (n > 64u) return (int)hipErrorInvalidValue;
+    void* kargs[] = {(void*)&p, (void*)&v, (void*)&n};
+    return (int)hipLaunchKernel((const void*)k_set_counters, dim3(1), dim3(64), kargs, 0, (hipStream_t)stream);
+}
+
 }  // namespace pbn

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define PBN_ABI_VERSION 15
+#define PBN_ABI_VERSION 16
 
 enum {
     PBN_OK = 0,
@@ -94,6 +94,8 @@ typedef struct {
                                count: pbn_env_handoffs */
     int32_t env_chunk;      /* last R6 env-step launch, env_kernel 2/4: updates per lane between draw rounds (32 or 48;
                                PBNSIM_ENV_CHUNK overrides) */
+    int32_t step_chains;    /* pbn_step: launch chains a call of two or more updates runs as (contiguous env ranges,
+                               one stream each, joined at the end of the call; PBNSIM_STEP_CHAINS forces 1, 2 or 4) */
 } pbn_batch_info;
 
 /* Attractor / goal description for the multi-flip env step (R6).
@@ -146,7 +148,7 @@ int pbn_net_select_u32(const pbn_net *net, int32_t node, uint32_t a, uint64_t *r
  * PBNSIM_ENV_LANES, PBNSIM_ENV_STEAL, PBNSIM_ENV_HELPERS, PBNSIM_ENV_GRID_STEAL, PBNSIM_ENV_KERNEL_IMAGE (R6 env kernel);
  * every one is set by a `-m gpu` test; A/B-only knobs are compiled in by -DPBN_MEASURE_KNOBS (tools/build_exp.sh);
  * PBNSIM_SSD_WAVE, PBNSIM_SSD_SERIAL, PBNSIM_SSD_SHARED (SSD); PBNSIM_ROLL_GROUP (rollout lanes per env);
- * PBNSIM_STEP_GRAPH=0 (pbn_step without HIP graphs); PBNSIM_MT_LANES=1 (MT-mode steps of predictor-mix networks
+ * PBNSIM_STEP_GRAPH=0 (pbn_step without HIP graphs); PBNSIM_STEP_CHAINS (pbn_step's launch chains); PBNSIM_MT_LANES=1 (MT-mode steps of predictor-mix networks
  * on k_mt_step's per-lane loads instead of k_mt_staged's LDS windows). */
 int pbn_batch_create(const pbn_net *net, int device, uint64_t n_envs, uint64_t env_id_base, uint64_t seed,
                      pbn_batch **out);
@@ -189,7 +191,14 @@ int pbn_flip_device(pbn_batch *b, const int32_t *d_actions, int A, int offset, i
  * (not on the null stream, nor with per-launch timing): one graph of exactly n_updates (<= 64)
  * launches when one is cached (pbn_step_prepare, or a call with the same n_updates as the previous
  * call), otherwise graphs of 64, 32, ..., 2 launches by the binary digits of n_updates. Larger batches
- * launch plainly (PBNSIM_STEP_GRAPH=0/1 overrides). Results are identical either way. */
+ * launch plainly (PBNSIM_STEP_GRAPH=0/1 overrides). Results are identical either way.
+ * Launch chains: a batch large enough for each half to fill the GPU (pbn_batch_info.step_chains == 2) runs a
+ * call of 128 or more updates as two chains of launches, one half of the envs each, chain 0 on the batch's
+ * stream (pbn_batch_set_stream's, if set) and the other on a stream of the batch's own; the call forks that
+ * stream off the batch's stream and joins it back, so anything queued on the batch's stream before or after the
+ * call keeps its order against the whole batch. Such a batch replays per-chain graphs below 2^24 state words.
+ * One chain: one update, per-launch timing, a call inside the caller's stream capture (the caller's graph gets
+ * a linear run of launches). PBNSIM_STEP_CHAINS=1/2/4 forces the count for every call of two or more updates. */
 int pbn_step(pbn_batch *b, uint32_t n_updates);
 /* Captures the graphs pbn_step(b, n_updates) will replay now (setup only: nothing runs, the state
  * is untouched): for n_updates <= 64 one graph of exactly that many launches (the batch keeps the

@@ -1,0 +1,23 @@
+"""The slice rule of step mode's launch chains (csrc/pbn_chain_split.hpp) under host sanitizers, on the CPU.
+
+``make chainsplitcheck`` compiles tests/host/chain_split_check.cpp (no HIP header, no library, no GPU) with
+ASan + UBSan and runs it: for every batch size up to 5,000, 1 / 2 / 4 chains and both step block sizes (and
+the bench sizes 2^20 and 2^23) the slices tile the batch in order, start at even envs, are never empty, and
+1M envs in two chains give two halves of 2^19.
+"""
+
+import shutil
+import subprocess
+from pathlib import Path
+
+import pytest
+
+ROOT = Path(__file__).resolve().parents[1]
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ is not installed")
+def test_chain_split_is_clean_under_asan_and_ubsan():
+    r = subprocess.run(["make", "-C", str(ROOT / "gym-pbn-stac_amd"), "chainsplitcheck"], capture_output=True,
+                       text=True)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "chain_split_check ok" in r.stdout
