@@ -85,22 +85,6 @@ static int roll_group_size(const pbn_batch* b, const pbn_net* net) {
     return 1;
 }
 
-// Envs from which one step launch fills every CU with 1024-thread workgroups.
-static uint64_t step_fill_envs(const pbn_batch* b) {
-    return (uint64_t)b->n_cu * 1024u * (uint64_t)b->knob.envs_per_thread;
-}
-
-// Launch chains of step mode by batch size (PBNSIM_STEP_CHAINS forces 1, 2 or 4; chain_split clamps to the
-// batch): two from the size at which each half still fills every CU with 1024-thread workgroups. One chain's
-// dispatch ramp, tail and kernel boundary then overlap the other chain's kernel. Measured on MI355X
-// (profiles/step_chains_ab.json, us per step, one chain -> two): Bittner-200 1M envs 5.9 -> 5.45, 2M
-// 12.6 -> 10.5, 4M 23.3 -> 19.8, 8M 45.0 -> 39.3; half that size (524,288 envs) 4.13 -> 4.37, and 65,536
-// Bittner-28 envs 3.03 -> 3.37: one chain there. Four chains were slower than two at every size.
-static int step_chains_for(const pbn_batch* b) {
-    if (b->knob.step_chains) return b->knob.step_chains;
-    return b->step_block == 1024 && b->B >= 2 * step_fill_envs(b) ? 2 : 1;
-}
-
 static int check_state_words(const pbn_batch* b, const uint64_t* w) {
     const int r = b->N & 63;
     if (!r) return 0;
@@ -250,17 +234,8 @@ int pbn_batch_create(const pbn_net* net_c, int device, uint64_t n_envs, uint64_t
     };
     if (hipGetDeviceProperties(&prop, device) != hipSuccess) return bail(fail(PBN_E_HIP, "hipGetDeviceProperties"));
     b->n_cu = prop.multiProcessorCount;
-    if (b->knob.step_block)
-        b->step_block = b->knob.step_block;
-    else  // 1024-thread groups stage the image 4x less often; small batches need more, smaller groups
-        b->step_block = n_envs >= step_fill_envs(b) ? 1024 : 256;
-    b->ch.n = chain_split(n_envs, step_chains_for(b), b->step_block, b->ch.sl);
-    b->ch.min_updates = b->knob.step_chains ? 2u : STEP_CHAIN_MIN_UPDATES;  // a forced count holds for every run
-    // two chains issue two launches per step: below STEP_CHAIN_GRAPH_MAX_WORDS the host does not keep up with
-    // them plainly, so a chained batch replays per-chain graphs up to there
-    b->sg.off = b->knob.step_graph >= 0 ? b->knob.step_graph == 0
-                                        : n_envs * (uint64_t)b->W >=
-                                              (b->ch.n > 1 ? STEP_CHAIN_GRAPH_MAX_WORDS : STEP_GRAPH_MAX_WORDS);
+    b->step = step_shape(n_envs, b->W, b->n_cu, b->knob.step_block, b->knob.step_chains, b->knob.step_graph,
+                         b->knob.envs_per_thread);
     // rollout lanes per env: 1 = k_rollout; 2/4/8 = k_rollout_grp (predictor mix, N <= 256)
     b->roll_group = roll_group_size(b, net);
     if (b->knob.roll_group >= 0) {
@@ -270,8 +245,8 @@ int pbn_batch_create(const pbn_net* net_c, int device, uint64_t n_envs, uint64_t
     if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess)
         return bail(fail(PBN_E_HIP, "hipStreamCreate"));
     b->own_stream = b->stream;
-    if (b->ch.n > 1) {  // the chains' streams right behind the batch's own
-        for (int c = 1; c < b->ch.n; ++c)
+    if (b->step.chains > 1) {  // the chains' streams right behind the batch's own
+        for (int c = 1; c < b->step.chains; ++c)
             if (hipStreamCreateWithFlags(&b->ch.stream[c], hipStreamNonBlocking) != hipSuccess ||
                 hipEventCreateWithFlags(&b->ch.done[c], hipEventDisableTiming) != hipSuccess)
                 return bail(fail(PBN_E_HIP, "step chain %d: stream / event create", c));
@@ -291,7 +266,7 @@ int pbn_batch_create(const pbn_net* net_c, int device, uint64_t n_envs, uint64_t
     if (!b->d_image) return bail(fail(PBN_E_NOMEM, "network image upload failed"));
     if ((rc = max_blocks_step(b->W, net->kind, net->L.bytes, BLOCK, &b->bpc_base)))
         return bail(fail(PBN_E_HIP, "occupancy query: %s", hipGetErrorString((hipError_t)rc)));
-    if ((rc = max_blocks_step(b->W, net->kind, net->L.plane_off, b->step_block, &b->bpc_step)))
+    if ((rc = max_blocks_step(b->W, net->kind, net->L.plane_off, b->step.block, &b->bpc_step)))
         return bail(fail(PBN_E_HIP, "occupancy query: %s", hipGetErrorString((hipError_t)rc)));
     if ((rc = max_blocks_step(b->W, net->kind, net->L.plane_off, BLOCK, &b->bpc_roll, 1, b->roll_group)))
         return bail(fail(PBN_E_HIP, "occupancy query: %s", hipGetErrorString((hipError_t)rc)));
@@ -303,37 +278,9 @@ void pbn_batch_destroy(pbn_batch* b) {
     if (!b) return;
     (void)hipSetDevice(b->device);
     if (b->stream) (void)hipStreamSynchronize(b->stream);
-    for (int c = 1; c < STEP_CHAINS_MAX; ++c) {  // every call joined its chains into `stream`: these are idle
-        if (b->ch.stream[c]) {
-            (void)hipStreamSynchronize(b->ch.stream[c]);
-            (void)hipStreamDestroy(b->ch.stream[c]);
-        }
-        if (b->ch.done[c]) (void)hipEventDestroy(b->ch.done[c]);
-    }
-    if (b->ch.fork) (void)hipEventDestroy(b->ch.fork);
-    for (auto& pr : b->tm.ev_pool) {
-        (void)hipEventDestroy(pr.first);
-        (void)hipEventDestroy(pr.second);
-    }
-    if (b->d_state) (void)hipFree(b->d_state);
-    if (b->d_nsteps) (void)hipFree(b->d_nsteps);
-    if (b->d_error) (void)hipFree(b->d_error);
-    for (DevBuf* d : {&b->s_act, &b->s_obs, &b->s_rew, &b->s_flags, &b->s_nup, &b->s_replay_i, &b->s_replay_k,
-                      &b->s_off, &b->s_mask, &b->mt.py, &b->mt.np, &b->mt.pos_py, &b->mt.pos_np, &b->mt.seeds,
-                      &b->r6.counter, &b->r6.steal, &b->r6.gpool, &b->aux.ssd_hist, &b->aux.ssd_tab, &b->aux.sync_tab, &b->sg.ubase, &b->s_flip_err})
-        d->release();
-    for (auto& chain : b->sg.graph)
-        for (hipGraphExec_t& g : chain)
-            if (g) (void)hipGraphExecDestroy(g);
-    for (auto& slot : b->sg.exact_graph)
-        for (hipGraphExec_t& g : slot)
-            if (g) (void)hipGraphExecDestroy(g);
-    b->pin.release();
-    if (b->own_stream) {
-        (void)hipStreamSynchronize(b->stream);
-        (void)hipStreamDestroy(b->own_stream);
-    }
-    delete b;
+    for (hipStream_t s : b->ch.stream)
+        if (s) (void)hipStreamSynchronize(s);
+    delete b;  // every member gives back what it holds (pbn_host.hpp)
 }
 
 int pbn_batch_set_stream(pbn_batch* b, int own, void* stream) {
@@ -368,7 +315,7 @@ int pbn_batch_get_info(const pbn_batch* b, pbn_batch_info* info) {
     info->env_lane_limit = (int)p.lane_limit;
     info->env_handoff = p.handoff ? 1 : 0;
     info->env_chunk = (p.mode == ENV_MODE_COOP || p.mode == ENV_MODE_TAIL) ? (int)p.chunk : 0;
-    info->step_chains = b->ch.n;
+    info->step_chains = b->step.chains;
     return 0;
 }
 

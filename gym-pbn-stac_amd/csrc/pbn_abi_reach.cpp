@@ -55,10 +55,6 @@ void pbn_reach_destroy(pbn_reach* r) {
     if (!r) return;
     (void)hipSetDevice(r->device);
     if (r->stream) (void)hipStreamSynchronize(r->stream);
-    for (DevBuf* d : {&r->keys, &r->mark, &r->table, &r->ctl, &r->queue, &r->free_ring, &r->hull, &r->in, &r->out})
-        d->release();
-    if (r->h_ctl) (void)hipHostFree(r->h_ctl);
-    if (r->stream) (void)hipStreamDestroy(r->stream);
     delete r;
 }
 

@@ -12,23 +12,40 @@ struct StepRange {
 };
 static StepRange whole_batch(const pbn_batch* b) { return {0, b->B, b->stream}; }
 static StepRange chain_range(const pbn_batch* b, int c, hipStream_t stream) {
-    return {b->ch.sl[c].off, b->ch.sl[c].len, stream};
+    return {b->step.sl[c].off, b->step.sl[c].len, stream};
 }
 
-static int step_launch(pbn_batch* b, const StepRange& r, uint32_t T, uint64_t update_base, int replay, const void* d_i,
-                       const void* d_k, const uint64_t* ubase_dev = nullptr, bool timed = true) {
+// What one launch of the step kernels runs: T updates from update_base, drawn from Philox -- or, with `node`,
+// along given node indices (replay: with their k53 draws; forced: without).
+struct StepWork {
+    uint32_t T = 1;
+    uint64_t update_base = 0;
+    bool timed = true;                    // ev_begin / ev_end around the launch
+    const uint64_t* ubase_dev = nullptr;  // inside a step graph: the update counter is *ubase_dev + update_base
+    const void* node = nullptr;
+    const void* k53 = nullptr;
+};
+static StepWork updates(uint32_t T, uint64_t update_base, bool timed = true) { return {T, update_base, timed}; }
+static StepWork graph_update(uint32_t k, const uint64_t* counter) { return {1, k, false, counter}; }
+static StepWork given_updates(uint32_t T, uint64_t update_base, const void* node, const void* k53) {
+    return {T, update_base, true, nullptr, node, k53};
+}
+
+static int step_launch(pbn_batch* b, const StepRange& r, const StepWork& w) {
+    const uint32_t T = w.T;
+    const bool replay = w.node != nullptr, timed = w.timed;
     StepArgs a{};
-    a.ubase_dev = ubase_dev;
+    a.ubase_dev = w.ubase_dev;
     a.state = b->d_state + r.off * (uint64_t)b->W;
     a.img = b->d_image;
     a.L = b->net->L;
     a.B = r.len;
     a.env_base = b->env_base + r.off;
     a.seed = b->seed;
-    a.update_base = update_base;
+    a.update_base = w.update_base;
     a.T = T;
-    a.replay_node = (const uint32_t*)d_i;
-    a.replay_k53 = (const uint64_t*)d_k;
+    a.replay_node = (const uint32_t*)w.node;
+    a.replay_k53 = (const uint64_t*)w.k53;
     hipEvent_t stop = nullptr;
     if (timed)
         if (int rc = b->ev_begin(&stop)) return rc;
@@ -40,7 +57,7 @@ static int step_launch(pbn_batch* b, const StepRange& r, uint32_t T, uint64_t up
     a.grp = rollout ? b->roll_group : 1;
     const uint64_t K = rollout ? 1u : (uint64_t)b->knob.envs_per_thread;
     const uint64_t lanes = rollout ? r.len * (uint64_t)a.grp : (r.len + K - 1) / K;
-    const int sb = (replay || rollout) ? BLOCK : b->step_block;
+    const int sb = (replay || rollout) ? BLOCK : b->step.block;
     const int grid = replay    ? b->grid_for(lanes, b->bpc_base)
                      : rollout ? b->grid_for(lanes, b->bpc_roll, sb)
                                : b->grid_for(lanes, b->bpc_step, sb);
@@ -51,83 +68,71 @@ static int step_launch(pbn_batch* b, const StepRange& r, uint32_t T, uint64_t up
 
 // Step mode is launch-bound between kernels (one HBM pass each): runs of step launches go out
 // as captured HIP graphs -- the same kernels with the same arguments, except that the update
-// counter comes from device memory (*ubase + k for launch k; k_bump adds the graph's length at
-// its end), so one instantiated graph per length serves every replay. Lengths 64, 32, ..., 2 are
-// all captured at the first call of two or more steps; a call of n steps replays 64-graphs, then
-// the binary digits of the rest (n = 20: the 16- and the 4-graph), then one plain launch if n is odd.
-static bool step_graph_ready(pbn_batch* b) {
+// counter comes from device memory (*ubase + k for launch k), so one instantiated graph per length
+// serves every replay. Which calls use them, and how a call is cut into replays: pbn_step_plan.hpp.
+//
+// Captures n step launches of chain c's envs -- and, with `bump`, a k_bump of the chain's counter by n behind
+// them -- into an instantiated exec, uploaded on `upload_on` if given. Captured on the batch's stream (a
+// captured launch keeps no stream); the launches read chain c's own counter, so one chain's k_bump never
+// races another chain's reads. A graph holds one chain only: it is a linear run of kernels.
+static bool capture_steps(pbn_batch* b, int c, uint32_t n, bool bump, hipStream_t upload_on, hipGraphExec_t* out) {
+    uint64_t* counter = (uint64_t*)b->sg.ubase.p + c;
+    const StepRange r = chain_range(b, c, b->stream);
+    hipGraph_t g = nullptr;
+    bool ok = hipStreamBeginCapture(b->stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
+    bool launched = ok;
+    for (uint32_t k = 0; launched && k < n; ++k) launched = step_launch(b, r, graph_update(k, counter)) == 0;
+    if (launched && bump) launched = launch_bump(counter, n, b->stream) == 0;
+    if (ok) ok = hipStreamEndCapture(b->stream, &g) == hipSuccess && launched && g;
+    if (ok) ok = hipGraphInstantiate(out, g, nullptr, nullptr, 0) == hipSuccess;
+    if (ok && upload_on) ok = hipGraphUpload(*out, upload_on) == hipSuccess;
+    if (g) (void)hipGraphDestroy(g);
+    return ok;
+}
+
+// A failed capture is not the caller's error: the call goes on with the graphs it has, or plain launches. The
+// family is marked, so later calls do not capture n launches to fail again.
+static void capture_failed(bool& family_broken) {
+    family_broken = true;
+    (void)hipGetLastError();
+    g_err.clear();
+}
+
+// The power-of-two graphs: lengths 64, 32, ..., 2 of every chain, with the k_bump that moves the chain's counter
+// on for the next replay of the call; all captured at the first call that replays one.
+static bool step_graph_ready(pbn_batch* b, bool may_capture) {
     if (b->sg.built) return true;
-    if (b->sg.broken || b->sg.off || !b->stream) return false;  // the null stream cannot capture
+    if (b->sg.broken || !may_capture) return false;
     if (b->sg.ubase.ensure(64)) return false;
     bool ok = true;
-    // every chain's graphs are captured on the batch's stream (a captured launch keeps no stream); chain c's
-    // read and bump its own counter, so one chain's k_bump never races another chain's reads
-    for (int c = 0; ok && c < b->ch.n; ++c)
-        for (int j = 0; ok && j < STEP_GRAPH_SIZES; ++j) {
-            const uint32_t K = STEP_GRAPH_K >> j;
-            uint64_t* counter = (uint64_t*)b->sg.ubase.p + c;
-            const StepRange r = chain_range(b, c, b->stream);
-            hipGraph_t g = nullptr;
-            ok = hipStreamBeginCapture(b->stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
-            bool launched = ok;
-            for (uint32_t k = 0; launched && k < K; ++k)
-                launched = step_launch(b, r, 1, k, 0, nullptr, nullptr, counter, false) == 0;
-            if (launched) launched = launch_bump(counter, K, b->stream) == 0;
-            if (ok) ok = hipStreamEndCapture(b->stream, &g) == hipSuccess && launched && g;
-            if (ok) ok = hipGraphInstantiate(&b->sg.graph[c][j], g, nullptr, nullptr, 0) == hipSuccess;
-            if (g) (void)hipGraphDestroy(g);
-        }
+    for (int c = 0; ok && c < b->step.chains; ++c)
+        for (int j = 0; ok && j < STEP_GRAPH_SIZES; ++j)
+            ok = capture_steps(b, c, STEP_GRAPH_K >> j, true, nullptr, &b->sg.graph[c][j]);
     if (!ok) {
-        for (auto& chain : b->sg.graph)
-            for (hipGraphExec_t& g : chain) {
-                if (g) (void)hipGraphExecDestroy(g);
-                g = nullptr;
-            }
-        b->sg.broken = true;
-        (void)hipGetLastError();  // the failed capture is not the caller's error
-        g_err.clear();
+        for (auto& chain : b->sg.graph) destroy_graph_execs(chain);
+        capture_failed(b->sg.broken);
         return false;
     }
     b->sg.built = true;
     return true;
 }
 
-// Captures n step launches as one graph in a free (or the least recently used) exact-length slot.
-// Returns the slot, or -1 (plain launches / power-of-two graphs then).
+// Captures n step launches as one graph per launch chain in a free (or the least recently used) exact-length
+// slot. Returns the slot, or -1 (plain launches / power-of-two graphs then).
 static int exact_graph_build(pbn_batch* b, uint32_t n) {
-    if (n < 2 || n > STEP_GRAPH_K || b->sg.broken || b->sg.off || b->sg.exact_broken || !b->stream)
-        return -1;
+    if (!step_exact_fits(n) || b->sg.broken || b->sg.exact_broken) return -1;
     if (b->sg.ubase.ensure(64)) return -1;
-    // capture and instantiate into a fresh exec first: a failed capture leaves the cached graphs
-    // as they were and marks the batch, so later calls do not re-capture n launches to fail again
+    // capture and instantiate into fresh execs first: a failed capture leaves the cached graphs as they were
     // no k_bump: pbn_step writes the device counter before every replay of an exact graph
-    // one graph per launch chain (each a linear run over that chain's envs), captured on the batch's stream
+    // upload now, on the stream that will replay it, so the first replay (e.g. a timed one) does not pay for it
     hipGraphExec_t x[STEP_CHAINS_MAX] = {};
     bool ok = true;
-    for (int c = 0; ok && c < b->ch.n; ++c) {
-        const StepRange r = chain_range(b, c, b->stream);
-        hipGraph_t g = nullptr;
-        ok = hipStreamBeginCapture(b->stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
-        bool launched = ok;
-        for (uint32_t k = 0; launched && k < n; ++k)
-            launched = step_launch(b, r, 1, k, 0, nullptr, nullptr, (const uint64_t*)b->sg.ubase.p + c, false) == 0;
-        if (ok) ok = hipStreamEndCapture(b->stream, &g) == hipSuccess && launched && g;
-        if (ok) ok = hipGraphInstantiate(&x[c], g, nullptr, nullptr, 0) == hipSuccess;
-        // upload now, on the stream that will replay it, so the first replay (e.g. a timed one) does not pay for it
-        if (ok) ok = hipGraphUpload(x[c], b->chain_stream(c)) == hipSuccess;
-        if (g) (void)hipGraphDestroy(g);
-    }
+    for (int c = 0; ok && c < b->step.chains; ++c) ok = capture_steps(b, c, n, false, b->chain_stream(c), &x[c]);
     // the extra chains' uploads are done before anything below may destroy an exec (setup, not a replay loop)
-    for (int c = 1; c < b->ch.n; ++c) (void)hipStreamSynchronize(b->ch.stream[c]);
-    auto drop = [&] {
-        for (hipGraphExec_t& e : x)
-            if (e) (void)hipGraphExecDestroy(e);
-    };
+    for (int c = 1; c < b->step.chains; ++c) (void)hipStreamSynchronize(b->ch.stream[c]);
     if (!ok) {
-        drop();
-        b->sg.exact_broken = true;
-        (void)hipGetLastError();
-        g_err.clear();
+        destroy_graph_execs(x);
+        capture_failed(b->sg.exact_broken);
         return -1;
     }
     int slot = 0;
@@ -138,12 +143,11 @@ static int exact_graph_build(pbn_batch* b, uint32_t n) {
         // (HIP documents no deferred free): drain the stream first -- every call joined its chains
         // into it. Eviction happens only at capture time, never in a steady replay loop.
         if (hipStreamSynchronize(b->stream) != hipSuccess) {
-            drop();
+            destroy_graph_execs(x);
             (void)fail(PBN_E_HIP, "stream sync before graph eviction failed");
             return -1;
         }
-        for (hipGraphExec_t& e : b->sg.exact_graph[slot])
-            if (e) (void)hipGraphExecDestroy(e);
+        destroy_graph_execs(b->sg.exact_graph[slot]);
     }
     for (int c = 0; c < STEP_CHAINS_MAX; ++c) b->sg.exact_graph[slot][c] = x[c];
     b->sg.exact_n[slot] = n;
@@ -165,7 +169,7 @@ static bool stream_capturing(pbn_batch* b) {
 
 // every chain's device counter <- update_count (one tiny kernel on the batch's stream, ahead of the fork)
 static int upload_update_count(pbn_batch* b) {
-    if (int e = launch_set_counters((uint64_t*)b->sg.ubase.p, b->update_count, (uint32_t)b->ch.n, b->stream))
+    if (int e = launch_set_counters((uint64_t*)b->sg.ubase.p, b->update_count, (uint32_t)b->step.chains, b->stream))
         return fail(PBN_E_HIP, "k_set_counters launch: %s", hipGetErrorString((hipError_t)e));
     return 0;
 }
@@ -173,16 +177,44 @@ static int upload_update_count(pbn_batch* b) {
 // A chained call's fork: the extra chains' streams wait for everything queued on the batch's stream so far.
 static int chains_fork(pbn_batch* b) {
     HIP_TRY(hipEventRecord(b->ch.fork, b->stream));
-    for (int c = 1; c < b->ch.n; ++c) HIP_TRY(hipStreamWaitEvent(b->ch.stream[c], b->ch.fork, 0));
+    for (int c = 1; c < b->step.chains; ++c) HIP_TRY(hipStreamWaitEvent(b->ch.stream[c], b->ch.fork, 0));
     return 0;
 }
 
 // ... and its join: whatever is queued on the batch's stream next waits for every chain's launches.
 static int chains_join(pbn_batch* b) {
-    for (int c = 1; c < b->ch.n; ++c) {
+    for (int c = 1; c < b->step.chains; ++c) {
         HIP_TRY(hipEventRecord(b->ch.done[c], b->ch.stream[c]));
         HIP_TRY(hipStreamWaitEvent(b->stream, b->ch.done[c], 0));
     }
+    return 0;
+}
+
+// Queues the launches of one pbn_step call: one exact graph, or the power-of-two graphs and the plain rest, or
+// plain launches only. A chained call queues each replay and each launch once per chain, alternating chains:
+// each chain's stream holds its own launches in update order.
+static int step_issue(pbn_batch* b, uint32_t n_updates, const StepCall& plan, int exact, bool pow2) {
+    const int S = plan.chained ? b->step.chains : 1;
+    if (exact >= 0) {
+        for (int c = 0; c < S; ++c) HIP_TRY(hipGraphLaunch(b->sg.exact_graph[exact][c], b->chain_stream(c)));
+        b->sg.exact_used[exact] = ++b->sg.exact_clock;
+        b->update_count += n_updates;
+        return 0;
+    }
+    StepPow2 d;
+    if (pow2) d = step_pow2(n_updates);
+    else d.plain = n_updates;
+    for (int j = 0; j < STEP_GRAPH_SIZES; ++j)
+        for (uint32_t q = 0; q < d.replays[j]; ++q) {
+            for (int c = 0; c < S; ++c) HIP_TRY(hipGraphLaunch(b->sg.graph[c][j], b->chain_stream(c)));
+            b->update_count += STEP_GRAPH_K >> j;
+        }
+    // a run's launches were accounted by pbn_step; any other call's launch takes its own event pair
+    for (uint32_t q = 0; q < d.plain; ++q, ++b->update_count)
+        for (int c = 0; c < S; ++c) {
+            const StepRange r = plan.chained ? chain_range(b, c, b->chain_stream(c)) : whole_batch(b);
+            if (int rc = step_launch(b, r, updates(1, b->update_count, !plan.run))) return rc;
+        }
     return 0;
 }
 
@@ -205,12 +237,10 @@ int pbn_step_prepare(pbn_batch* b, uint32_t n_updates) {
     if (n_updates > PBN_STEP_PREPARE_MAX)
         return fail(PBN_E_INVALID, "n_updates=%u above PBN_STEP_PREPARE_MAX", n_updates);
     SET_DEV(b);
-    if (n_updates < 2 || b->sg.off || stream_capturing(b)) return 0;
-    if (b->ch.n > 1 && n_updates < b->ch.min_updates) return 0;  // an unsplit call of a batch with chains: plain launches
-    // on failure pbn_step falls back to plain launches; runs longer than STEP_GRAPH_K replay the
-    // power-of-two graphs (one graph of thousands of launches replayed slower: 3.43 vs 3.16 us per
-    // launch at 65,536 Bittner-28 envs)
-    if (n_updates > STEP_GRAPH_K) (void)step_graph_ready(b);
+    // the call this prepares comes later, in a timing mode of its own: planned as an untimed one. On a failed
+    // capture pbn_step falls back to plain launches
+    if (!step_call(b->step, n_updates, 0, stream_capturing(b), !b->stream).capture) return 0;
+    if (!step_exact_fits(n_updates)) (void)step_graph_ready(b, true);
     else if (exact_graph_find(b, n_updates) < 0) (void)exact_graph_build(b, n_updates);
     return 0;
 }
@@ -218,82 +248,28 @@ int pbn_step_prepare(pbn_batch* b, uint32_t n_updates) {
 int pbn_step(pbn_batch* b, uint32_t n_updates) {
     CHECK_NN(b, "batch");
     SET_DEV(b);
-    uint32_t t = 0;
-    // not while the caller is capturing the stream into a graph of its own: plain launches then
-    const bool cap = stream_capturing(b);
-    const uint32_t smallest = STEP_GRAPH_K >> (STEP_GRAPH_SIZES - 1);
-    // a run: two or more updates, no event pair per launch, not inside the caller's capture. Only a run
-    // replays graphs, and only a run is split into the batch's launch chains.
-    const bool run = !cap && b->tm.mode != 1 && n_updates >= 2;
-    const bool chained = run && b->ch.n > 1 && n_updates >= b->ch.min_updates;
-    const int S = chained ? b->ch.n : 1;
-    // the graphs of a batch with chains cover the chains' slices: its unsplit calls launch plainly
-    const bool graphs = run && !b->sg.off && (b->ch.n == 1 || chained);
+    const StepCall plan = step_call(b->step, n_updates, b->tm.mode, stream_capturing(b), !b->stream);
     int exact = -1;
-    if (graphs) {
+    if (plan.graphs) {
         exact = exact_graph_find(b, n_updates);
         // a length seen twice in a row gets its own graph (an RL loop's fixed step count)
-        if (exact < 0 && n_updates == b->sg.last_n && n_updates <= STEP_GRAPH_K)
-            exact = exact_graph_build(b, n_updates);
+        if (exact < 0 && plan.capture && n_updates == b->sg.last_n) exact = exact_graph_build(b, n_updates);
     }
     b->sg.last_n = n_updates;
-    const bool pow2 = exact < 0 && graphs && n_updates >= smallest && step_graph_ready(b);
+    const bool pow2 = plan.graphs && exact < 0 && step_graph_ready(b, plan.capture);
     if (exact >= 0 || pow2)
         if (int rc = upload_update_count(b)) return rc;
-    if (chained) {
-        // the call counts as n_updates launches (one per step, not per chain); the region's start, like its
-        // stop, is recorded on the batch's stream: ahead of the fork, behind the join
-        if (b->tm.mode == 2) {
-            hipEvent_t stop;
-            if (int rc = b->ev_begin(&stop)) return rc;
-            b->tm.region_launches += n_updates - 1;  // ev_begin counted one
-        }
-        if (int rc = chains_fork(b)) return rc;
-    }
-    // k updates about to be queued as one graph replay (per chain)
-    auto count = [&](uint32_t k) -> int {
-        if (chained) return 0;
-        hipEvent_t stop;  // stays null: no graph replays in timing mode 1
+    // a run counts as n_updates launches (one per step, not per replay or per chain), all accounted here; the
+    // region's start, like its stop, is recorded on the batch's stream: ahead of the fork, behind the join
+    if (plan.run && b->tm.mode == 2) {
+        hipEvent_t stop;  // stays null: a region's stop is recorded when it closes
         if (int rc = b->ev_begin(&stop)) return rc;
-        if (b->tm.mode == 2) b->tm.region_launches += k - 1;  // ev_begin counted one
-        return 0;
-    };
-    // the host alternates chains replay by replay and launch by launch: each chain's stream holds its own
-    // launches in update order
-    auto queue = [&]() -> int {
-        if (exact >= 0) {
-            if (int rc = count(n_updates)) return rc;
-            for (int c = 0; c < S; ++c) HIP_TRY(hipGraphLaunch(b->sg.exact_graph[exact][c], b->chain_stream(c)));
-            b->sg.exact_used[exact] = ++b->sg.exact_clock;
-            b->update_count += n_updates;
-            return 0;
-        }
-        if (pow2) {
-            for (int j = 0; j < STEP_GRAPH_SIZES; ++j) {
-                const uint32_t K = STEP_GRAPH_K >> j;
-                while (n_updates - t >= K && (j == 0 || n_updates - t < 2 * K)) {
-                    if (int rc = count(K)) return rc;
-                    for (int c = 0; c < S; ++c) HIP_TRY(hipGraphLaunch(b->sg.graph[c][j], b->chain_stream(c)));
-                    b->update_count += K;
-                    t += K;
-                }
-            }
-        }
-        for (; t < n_updates; t++) {
-            if (!chained) {
-                if (int rc = step_launch(b, whole_batch(b), 1, b->update_count, 0, nullptr, nullptr)) return rc;
-            } else {
-                for (int c = 0; c < S; ++c)
-                    if (int rc = step_launch(b, chain_range(b, c, b->chain_stream(c)), 1, b->update_count, 0, nullptr,
-                                             nullptr, nullptr, false))
-                        return rc;
-            }
-            b->update_count++;
-        }
-        return 0;
-    };
-    int rc = queue();
-    if (chained) {  // also after a failed launch: what was queued on the chains stays ordered
+        b->tm.region_launches += n_updates - 1;  // ev_begin counted one
+    }
+    if (plan.chained)
+        if (int rc = chains_fork(b)) return rc;
+    int rc = step_issue(b, n_updates, plan, exact, pow2);
+    if (plan.chained) {  // also after a failed launch: what was queued on the chains stays ordered
         const int jrc = chains_join(b);
         if (!rc) rc = jrc;
     }
@@ -304,7 +280,7 @@ int pbn_rollout(pbn_batch* b, uint32_t n_updates) {
     CHECK_NN(b, "batch");
     if (!n_updates) return 0;
     SET_DEV(b);
-    if (int rc = step_launch(b, whole_batch(b), n_updates, b->update_count, 0, nullptr, nullptr)) return rc;
+    if (int rc = step_launch(b, whole_batch(b), updates(n_updates, b->update_count))) return rc;
     b->update_count += n_updates;
     return 0;
 }
@@ -321,7 +297,7 @@ int pbn_step_replay(pbn_batch* b, const uint32_t* node_idx, const uint64_t* k53,
     if (int rc = b->s_replay_k.ensure(8 * n)) return rc;
     HIP_TRY(hipMemcpyAsync(b->s_replay_i.p, node_idx, 4 * n, hipMemcpyHostToDevice, b->stream));
     HIP_TRY(hipMemcpyAsync(b->s_replay_k.p, k53, 8 * n, hipMemcpyHostToDevice, b->stream));
-    if (int rc = step_launch(b, whole_batch(b), n_updates, 0, 1, b->s_replay_i.p, b->s_replay_k.p)) return rc;
+    if (int rc = step_launch(b, whole_batch(b), given_updates(n_updates, 0, b->s_replay_i.p, b->s_replay_k.p))) return rc;
     HIP_TRY(hipStreamSynchronize(b->stream));
     return 0;
 }
@@ -337,7 +313,7 @@ int pbn_step_forced(pbn_batch* b, const uint32_t* node_idx, uint32_t n_updates) 
     HIP_TRY(hipMemcpyAsync(b->s_replay_i.p, node_idx, 4 * n, hipMemcpyHostToDevice, b->stream));
     // replay-mode kernel with no k53 array: update t takes the choice word of Philox step update
     // update_count + t (the draw pbn_step would use), so the stream stays in step with pbn_step
-    if (int rc = step_launch(b, whole_batch(b), n_updates, b->update_count, 1, b->s_replay_i.p, nullptr)) return rc;
+    if (int rc = step_launch(b, whole_batch(b), given_updates(n_updates, b->update_count, b->s_replay_i.p, nullptr))) return rc;
     b->update_count += n_updates;
     HIP_TRY(hipStreamSynchronize(b->stream));  // the staging buffer is reused by the next call
     return 0;

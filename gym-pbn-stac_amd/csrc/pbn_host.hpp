@@ -17,8 +17,8 @@
 #endif
 
 #include "../../include/pbn_abi.h"
-#include "pbn_chain_split.hpp"
 #include "pbn_params.hpp"
+#include "pbn_step_plan.hpp"
 
 using namespace pbn;
 
@@ -82,9 +82,15 @@ PBN_HIDDEN uint64_t net_select_u32(const pbn_net* n, int32_t node, uint32_t a);
     } while (0)
 #define SET_DEV(b) HIP_TRY(hipSetDevice((b)->device))
 
+// Device memory, pinned host memory, streams, events and graph execs are given back by the destructor of the
+// object that holds them, with the object's device current (pbn_batch_destroy, pbn_reach_destroy).
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
     int ensure(size_t bytes) {
         if (bytes <= cap) return 0;
         release();
@@ -105,6 +111,10 @@ struct DevBuf {
 struct PinBuf {
     static constexpr size_t CAP = 64 * 1024;
     uint8_t* p = nullptr;
+    PinBuf() = default;
+    PinBuf(const PinBuf&) = delete;
+    PinBuf& operator=(const PinBuf&) = delete;
+    ~PinBuf() { release(); }
     bool ready() {
         if (!p && hipHostMalloc((void**)&p, CAP, hipHostMallocDefault) != hipSuccess) p = nullptr;
         return p != nullptr;
@@ -114,6 +124,14 @@ struct PinBuf {
         p = nullptr;
     }
 };
+
+template <size_t N>
+inline void destroy_graph_execs(hipGraphExec_t (&x)[N]) {
+    for (hipGraphExec_t& g : x) {
+        if (g) (void)hipGraphExecDestroy(g);
+        g = nullptr;
+    }
+}
 
 // The device-open prologue of pbn_batch_create and pbn_reach_create.
 inline int open_device(int device) {
@@ -132,18 +150,6 @@ inline int check_action_shape(int A, int offset) {
     if (offset != 0 && offset != 1) return fail(PBN_E_INVALID, "offset must be 0 or 1");
     return 0;
 }
-
-constexpr uint32_t STEP_GRAPH_K = 64;  // longest captured run of step launches
-constexpr int STEP_GRAPH_SIZES = 6;     // graphs of 64, 32, 16, 8, 4 and 2 launches
-constexpr uint64_t STEP_GRAPH_MAX_WORDS = 1ull << 20;  // state words from which step mode launches plainly
-// ... and from which a batch stepped as two or more launch chains does: each step is one launch per chain, and
-// the host issues plain launches at 3.3-4.4 us each (1M Bittner-200 envs, two chains: 8.5 us per step plain,
-// 5.45 as graphs; 2M: 11.6 vs 10.5; 4M: 19.8 vs 20.5)
-constexpr uint64_t STEP_CHAIN_GRAPH_MAX_WORDS = 1ull << 24;
-// Updates from which a call is split into the chains chosen by size: the fork, the join and a graph start per
-// chain cost a call about 20 us (1M Bittner-200 envs, bench.py --warmup 5, us per step, one chain -> two:
-// 20 steps 9.7 -> 10.6, 64 steps 8.8 -> 8.7, 200 steps 8.0 -> 7.5; 1,000 steps after 200: 6.5 -> 5.9)
-constexpr uint32_t STEP_CHAIN_MIN_UPDATES = 128;
 
 // Launch knobs read from PBNSIM_* once at pbn_batch_create (read_knobs, pbn_abi.cpp): measurement / tests.
 struct Knobs {
@@ -206,18 +212,14 @@ struct pbn_batch {
     int32_t* d_error = nullptr;
     const void* d_image = nullptr;
     int n_cu = 0, bpc_step = 1, bpc_base = 1, bpc_roll = 1;
-    int step_block = 1024;  // threads per workgroup of the Philox step kernel (256 or 1024)
-    int roll_group = 1;     // lanes per env of the rollout kernel
+    StepShape step;      // step mode's block, launch chains and graphs on / off (pbn_step_plan.hpp)
+    int roll_group = 1;  // lanes per env of the rollout kernel
     Knobs knob;
     PinBuf pin;                         // staging for small host<->device copies
     DevBuf s_flip_err;                  // range-error flag of pbn_flip_device
     DevBuf s_act, s_obs, s_rew, s_flags, s_nup, s_replay_i, s_replay_k, s_off, s_mask;
 
     struct StepGraphs {
-        // step mode without HIP graphs: by default for large batches (a graph replay's start on the
-        // device costs more than host submission, which a long kernel hides: 1M Bittner-200 envs, 20
-        // launches: 9.3 us per launch plain vs 9.9 us as one replay); PBNSIM_STEP_GRAPH=0/1 forces it
-        bool off = false;
         // graph[c][j]: (STEP_GRAPH_K >> j) step launches of chain c's envs + k_bump on chain c's counter,
         // captured once (all sizes and chains at the first call of two or more steps). A graph holds one
         // chain only: it is a linear run of kernels.
@@ -234,17 +236,25 @@ struct pbn_batch {
         uint64_t exact_clock = 0;
         uint32_t last_n = 0;
         DevBuf ubase;  // device copies of update_count for graph replays, one 8-byte counter per chain
+        ~StepGraphs() {
+            for (auto& chain : graph) destroy_graph_execs(chain);
+            for (auto& slot : exact_graph) destroy_graph_execs(slot);
+        }
     } sg;
-    // Launch chains of step mode (pbn_step): chain c steps the envs of sl[c] on its own stream, chain 0 on
+    // Launch chains of step mode (pbn_step): chain c steps the envs of step.sl[c] on its own stream, chain 0 on
     // `stream`. A call forks the extra streams off `stream` and joins them back into it, so everything else
     // queued on `stream` keeps its order against the whole batch.
     struct Chains {
-        int n = 1;                                   // chains in use (pbn_batch_info.step_chains)
-        uint32_t min_updates = 2;                    // calls of fewer updates run as one chain (2 = every run)
-        ChainSlice sl[STEP_CHAINS_MAX];              // sl[0 .. n): the batch in order
-        hipStream_t stream[STEP_CHAINS_MAX] = {};    // [1 .. n): the batch's own, non-blocking; [0] unused
-        hipEvent_t done[STEP_CHAINS_MAX] = {};       // [1 .. n): end of chain c's launches of a call
+        hipStream_t stream[STEP_CHAINS_MAX] = {};  // [1 .. step.chains): the batch's own, non-blocking; [0] unused
+        hipEvent_t done[STEP_CHAINS_MAX] = {};     // [1 .. step.chains): end of chain c's launches of a call
         hipEvent_t fork = nullptr;
+        ~Chains() {  // every call joined its chains into `stream`, and pbn_batch_destroy waited: these are idle
+            for (hipStream_t s : stream)
+                if (s) (void)hipStreamDestroy(s);
+            for (hipEvent_t e : done)
+                if (e) (void)hipEventDestroy(e);
+            if (fork) (void)hipEventDestroy(fork);
+        }
     } ch;
     hipStream_t chain_stream(int c) const { return c ? ch.stream[c] : stream; }
     struct R6 {
@@ -276,7 +286,20 @@ struct pbn_batch {
         bool region_closed = false;
         hipEvent_t region_start = nullptr;  // ev_pool[0].first once the region's first launch is queued
         hipEvent_t region_end = nullptr;    // the closed region's stop event
+        ~Timing() {
+            for (auto& pr : ev_pool) {
+                (void)hipEventDestroy(pr.first);
+                (void)hipEventDestroy(pr.second);
+            }
+        }
     } tm;
+
+    ~pbn_batch() {  // pbn_batch_destroy: the device is current and the streams have drained
+        if (d_state) (void)hipFree(d_state);
+        if (d_nsteps) (void)hipFree(d_nsteps);
+        if (d_error) (void)hipFree(d_error);
+        if (own_stream) (void)hipStreamDestroy(own_stream);
+    }
 
     int grid_for(uint64_t items, int bpc, int block = BLOCK) const {
         uint64_t need = (items + block - 1) / block;
@@ -348,6 +371,11 @@ struct pbn_reach {
     uint32_t count = 0;         // live entries
     uint32_t epoch = 0;         // of the last mark_backward (0: none since the closure)
     bool complete = false;
+
+    ~pbn_reach() {  // pbn_reach_destroy: the device is current and the stream has drained
+        if (h_ctl) (void)hipHostFree(h_ctl);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
 
     ReachArgs args() const {
         ReachArgs a{};

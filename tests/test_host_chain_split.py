@@ -21,3 +21,14 @@ def test_chain_split_is_clean_under_asan_and_ubsan():
                        text=True)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "chain_split_check ok" in r.stdout
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ is not installed")
+def test_step_plan_is_clean_under_asan_and_ubsan():
+    """``make stepplancheck``: tests/host/step_plan_check.cpp on csrc/pbn_step_plan.hpp, the same way. The batch
+    shape and the call plan against a restatement of their rules either side of every size threshold, and the
+    power-of-two decomposition of every call length up to 5,000 against the greedy loop it replaced."""
+    r = subprocess.run(["make", "-C", str(ROOT / "gym-pbn-stac_amd"), "stepplancheck"], capture_output=True,
+                       text=True)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "step_plan_check ok" in r.stdout

@@ -89,9 +89,11 @@ def test_timing_counts_steps_not_chain_launches(G, monkeypatch, chains):
     b.step(20)
     b.step(1)
     b.step(20)
+    b.step(65)  # a 64-replay and a plain launch
+    b.step(130)  # two 64-replays and a 2-replay
     b.timing(0)
     ms, launches = b.timing_read()
-    assert launches == 41 and ms > 0
+    assert launches == 236 and ms > 0
     b.timing(1)  # an event pair per launch: one whole-batch launch per step
     b.step(5)
     b.step(1)
