@@ -38,15 +38,15 @@ static Knobs read_knobs() {
     if (const char* sm = getenv("PBNSIM_STORE_MODE")) k.store_mode = atoi(sm) ? STORE_DIRTY : STORE_FULL;
     if (const char* r = getenv("PBNSIM_ENVS_PER_THREAD")) k.envs_per_thread = std::max(1, std::min(64, atoi(r)));
     if (const char* v = getenv("PBNSIM_STEP_BLOCK")) k.step_block = atoi(v) == 256 ? 256 : 1024;
-    k.env_no_gen = getenv("PBNSIM_ENV_NO_GEN") != nullptr;
-    if (const char* v = getenv("PBNSIM_ENV_GROUP")) k.env_group = std::max(1, atoi(v));
-    if (const char* v = getenv("PBNSIM_ENV_BPC")) k.env_bpc = std::max(1, atoi(v));
-    if (const char* v = getenv("PBNSIM_ENV_CHUNK")) k.env_chunk = atoi(v);
-    if (const char* v = getenv("PBNSIM_ENV_GRID")) k.env_grid_cap = std::max(1, atoi(v));
-    if (const char* v = getenv("PBNSIM_ENV_TAIL")) k.env_tail = std::max(0, std::min(64, atoi(v)));
-    if (const char* v = getenv("PBNSIM_ENV_LANES")) k.env_lane_limit = std::max(0, std::min(64, atoi(v)));
-    if (const char* v = getenv("PBNSIM_ENV_STEAL")) k.env_steal = atoi(v) != 0;
-    if (const char* v = getenv("PBNSIM_ENV_KERNEL_IMAGE")) k.env_kernel_image = atoi(v) != 0;
+    k.env.no_gen = getenv("PBNSIM_ENV_NO_GEN") != nullptr;
+    if (const char* v = getenv("PBNSIM_ENV_GROUP")) k.env.group = std::max(1, atoi(v));
+    if (const char* v = getenv("PBNSIM_ENV_BPC")) k.env.bpc = std::max(1, atoi(v));
+    if (const char* v = getenv("PBNSIM_ENV_CHUNK")) k.env.chunk = atoi(v);
+    if (const char* v = getenv("PBNSIM_ENV_GRID")) k.env.grid_cap = std::max(1, atoi(v));
+    if (const char* v = getenv("PBNSIM_ENV_TAIL")) k.env.tail = std::max(0, std::min(64, atoi(v)));
+    if (const char* v = getenv("PBNSIM_ENV_LANES")) k.env.lane_limit = std::max(0, std::min(64, atoi(v)));
+    if (const char* v = getenv("PBNSIM_ENV_STEAL")) k.env.steal = atoi(v) != 0;
+    if (const char* v = getenv("PBNSIM_ENV_KERNEL_IMAGE")) k.env.kernel_image = atoi(v) != 0;
     if (const char* v = getenv("PBNSIM_ENV_HELPERS")) k.env_helpers = std::max(0, std::min(3, atoi(v)));
     if (const char* v = getenv("PBNSIM_ENV_GRID_STEAL")) k.env_grid_steal = atoi(v) != 0 ? 1 : 0;
 #ifdef PBN_MEASURE_KNOBS  // A/B-only knobs: tools/build_exp.sh -DPBN_MEASURE_KNOBS
@@ -311,7 +311,7 @@ int pbn_batch_get_info(const pbn_batch* b, pbn_batch_info* info) {
     info->env_lanes = p.grp;
     info->roll_lanes = b->roll_group;
     info->env_grid = p.grid;
-    info->env_kernel = p.kernel;
+    info->env_kernel = p.mode;
     info->env_lane_limit = (int)p.lane_limit;
     info->env_handoff = p.handoff ? 1 : 0;
     info->env_chunk = (p.mode == ENV_MODE_COOP || p.mode == ENV_MODE_TAIL) ? (int)p.chunk : 0;

@@ -1,4 +1,4 @@
-// pbn_abi_env.cpp -- R6: env reset, the env-step launch (env_plan decides, env_launch launches), the four
+// pbn_abi_env.cpp -- R6: env reset, the env-step launch (env_plan, pbn_env_plan.hpp, decides; env_launch launches), the four
 // pbn_env_step* / rollout entry points and the hand-off / grid-pool statistics.
 #include "pbn_host.hpp"
 
@@ -16,116 +16,45 @@ static int env_reset(pbn_batch* b, const pbn_envcfg* cfg_c, const void* d_mask) 
     if (cfg->H_reset < 1) return fail(PBN_E_STATE, "envcfg has no reset cubes (all_attractors[0])"); \
     SET_DEV(b)
 
-// Lanes per env for the R6 kernel: 1 (lane mode, k_env) while the batch fills the chip
-// several times over; group mode where it does not and the until-attractor tail would
-// leave lanes idle (measured: DESIGN.md section 6).
-// Per-step call, Bittner-200, 1 MI355X (256 CUs): G = 8 beats lane mode up to 32k envs (0.21 vs
-// 0.33 ms at B = 1, 0.88 vs 1.99 ms at 8k, 1.85 vs 2.04 ms at 32k) and loses from 64k on (2.31 vs
-// 2.07 ms; 131k: 3.28 vs 2.60 ms) -- the crossover sits near 48k envs.
-// Group mode (G = 8 lanes per env) for small batches -- except where the tail kernel (k_env ENV_MODE_TAIL:
-// <= 4 cubes and its 16-B env records fit) applies: its tail mode with one env per wave
-// (env_lane_limit) is faster at every batch size measured (profiles/r03_r6_lanes_sweep.json)
-static int env_group_size(const pbn_batch* b, bool tail_kernel) {
-    if (tail_kernel) return 1;
-    return b->B * 8 <= (uint64_t)b->n_cu * 1536 ? 8 : 1;
+// One R6 launch as its entry point asked for it; env_plan_in and env_launch read the same one.
+struct EnvCall {
+    int A, dedup, offset;
+    uint32_t cap;  // updates per env step
+    int replay;
+    uint32_t n_calls;  // env steps per env
+};
+
+// replay mode has no update cap: an env step ends with its recorded draws
+constexpr uint32_t REPLAY_NO_CAP = 0xFFFFFFFFu;
+
+// The plan's inputs (pbn_env_plan.hpp): the one place that reads the batch and the env config for the decision.
+static EnvPlanIn env_plan_in(const pbn_batch* b, const pbn_envcfg* cfg, const EnvCall& c) {
+    EnvPlanIn in;
+    in.B = b->B;
+    in.W = b->W;
+    in.N = b->net->N;
+    in.kind = b->net->kind;
+    in.n_cu = b->n_cu;
+    in.counters_ok = cfg->counters_ok;
+    in.H = cfg->H;
+    in.pmax = cfg->L.pmax;
+    in.image_bytes = cfg->L.bytes;
+    in.off_rec = cfg->L.off_rec;
+    in.off_cubes = cfg->off_cubes;
+    in.rs = thr32_layout(cfg->L).rs;
+    in.replay = c.replay != 0;
+    in.cap = c.cap;
+    in.n_calls = c.n_calls;
+    in.knob = b->knob.env;
+    in.grid_steal = b->knob.env_grid_steal;
+    return in;
 }
 
-// The decision half of an R6 launch: kernel mode, geometry and hand-offs. Reads the batch and the env config
-// and queries occupancy; writes no buffer and does not touch the stream. p.error: a failed occupancy query.
-static EnvPlan env_plan(const pbn_batch* b, const pbn_envcfg* cfg, int replay, uint32_t cap, uint32_t n_calls) {
-    EnvPlan p;
-    const Knobs& k = b->knob;
-    // cooperative draw generation: predictor mix, Philox, record index fits the u16 entry
-    int mode = (cfg->fast && !replay && b->net->kind == KIND_PREDICTOR_MIX && cfg->L.pmax <= 16 &&
-                b->net->N <= 512 && !k.env_no_gen)
-                   ? (int)ENV_MODE_COOP
-                   : cfg->fast;
-    // cooperative-draw mode keeps 16-B env records in LDS where the 8-B predictor records were
-    // (env_record_words, pbn_params.hpp): the tables after them move up by erec_shift. Whether they fit is
-    // decided first, so that the group-size rule below knows whether the tail kernel (ENV_MODE_TAIL) applies
-    uint32_t erec_shift = 0;
-    bool erec_fits = false;
-    if (mode == ENV_MODE_COOP) {
-        // rows of rs records (thr32_layout: tp4 + 1 slots at least, for the saturated choice)
-        const uint32_t nrec = (uint32_t)b->net->N * thr32_layout(cfg->L).rs;
-        erec_shift = cfg->L.off_rec + 16u * nrec - cfg->off_cubes;
-        erec_fits = nrec <= 65535u &&
-                    env_lds_bytes(b->W, cfg->L.bytes + erec_shift, ENV_MODE_COOP, 1, ENV_CHUNK_SMALL) <= ENV_LDS_MAX;
-    }
-    // group mode (k_env_grp: G lanes per env, G updates per round trip; its rows need no env records)
-    int grp = 1;
-    if (mode == ENV_MODE_COOP && b->net->N <= 256) {
-        grp = k.env_group ? k.env_group : env_group_size(b, erec_fits && cfg->H <= 4);
-        if (grp != 2 && grp != 4 && grp != 8) grp = 1;
-        if (grp > 1) mode = ENV_MODE_GROUP;
-    }
-    if (mode == ENV_MODE_COOP) {
-        if (!erec_fits)
-            mode = cfg->fast;  // too large for the u16 record index / one workgroup's LDS
-        else if (cfg->H <= 4)
-            mode = ENV_MODE_TAIL;  // the same kernel with one packed counter word (<= 4 cubes)
-        // ENV_MODE_TAIL adds the workgroup hand-off control words: re-check the fit with the final mode
-        if (mode == ENV_MODE_TAIL &&
-            env_lds_bytes(b->W, cfg->L.bytes + erec_shift, ENV_MODE_TAIL, 1, ENV_CHUNK_SMALL) > ENV_LDS_MAX)
-            mode = cfg->fast;
-    }
-    const bool coop = mode == ENV_MODE_COOP || mode == ENV_MODE_TAIL;
-    if (!coop) erec_shift = 0;
-    const uint32_t img = cfg->L.bytes + erec_shift;
-    // PBNSIM_ENV_KERNEL_IMAGE=1: the kernel builds its LDS image itself (tests keep that path covered)
-    p.host_image = coop && img % 16u == 0u && !k.env_kernel_image;
-    int bpc = 1;
-    uint32_t chunk = ENV_CHUNK_SMALL;
-    if (coop) {
-        // the draw-round chunk (pbn_params.hpp ENV_CHUNK_SMALL / _LARGE): the large one unless the small
-        // one's draw buffers let more workgroups onto a CU and the launch is a throughput-bound fused run
-        // (>= 16 env steps per env over a queue of >= 4 envs per lane of the large one's grid), or the large
-        // one does not fit one workgroup's 64 KiB; PBNSIM_ENV_CHUNK=32 / 48 overrides
-        int bpc_s = 1, bpc_l = 1;
-        p.error = max_blocks_env(b->W, b->net->kind, mode, grp, img, &bpc_s, ENV_CHUNK_SMALL);
-        const bool large_fits = env_lds_bytes(b->W, img, mode, 1, ENV_CHUNK_LARGE) <= ENV_LDS_MAX;
-        if (large_fits && !p.error)
-            p.error = max_blocks_env(b->W, b->net->kind, mode, grp, img, &bpc_l, ENV_CHUNK_LARGE);
-        const uint64_t lanes_l = (uint64_t)b->n_cu * (uint64_t)bpc_l * ENV_BLOCK;
-        const bool throughput = n_calls >= 16u && b->B >= 4u * lanes_l && bpc_s > bpc_l;
-        chunk = large_fits && !throughput ? ENV_CHUNK_LARGE : ENV_CHUNK_SMALL;
-        if (k.env_chunk == (int)ENV_CHUNK_SMALL || (k.env_chunk == (int)ENV_CHUNK_LARGE && large_fits))
-            chunk = (uint32_t)k.env_chunk;
-        bpc = chunk == ENV_CHUNK_LARGE ? bpc_l : bpc_s;
-    } else {
-        p.error = max_blocks_env(b->W, b->net->kind, mode, grp, img, &bpc);
-    }
-    if (k.env_bpc) bpc = std::min(bpc, k.env_bpc);
-    p.tail_max = k.env_tail >= 0 ? (uint32_t)k.env_tail : ENV_TAIL_DEFAULT;
-    // tail-mode kernel: small batches (ENV_ONE_LANE_ENVS_PER_SLOT envs per wave slot) take one env per
-    // wave at a time -- every wave resolves its env 64 updates per block and takes the next from the
-    // queue when it is done (PBNSIM_ENV_LANES overrides; 64 = lane mode, the tail at the end)
-    p.lane_limit = 64u;
-    if (mode == ENV_MODE_TAIL) {
-        const uint64_t slots = (uint64_t)b->n_cu * (uint64_t)bpc * (ENV_BLOCK / 64);
-        if (k.env_lane_limit > 0)
-            p.lane_limit = (uint32_t)k.env_lane_limit;
-        else if (p.tail_max >= 1 && b->B <= ENV_ONE_LANE_ENVS_PER_SLOT * slots)
-            p.lane_limit = 1u;
-    }
-    // lanes per env (group mode) or, with a lane limit, 64 / limit lane slots per env
-    p.grid = b->grid_for(p.lane_limit < 64u ? (b->B * 64u + p.lane_limit - 1u) / p.lane_limit : b->B * (uint64_t)grp, bpc,
-                         env_block(mode));
-    // PBNSIM_ENV_GRID: exactly that many workgroups (at most the resident count; persistent waves: any grid
-    // drains the counter, and surplus workgroups find the queue empty)
-    if (k.env_grid_cap) p.grid = std::min(k.env_grid_cap, b->n_cu * bpc);
-    // tail hand-off (k_env ENV_MODE_TAIL): a wave holding several envs in tail mode passes envs it has not
-    // started on to idle waves of its workgroup (LDS). One lane per wave taking envs (small batches)
-    // never holds two: off there
-    p.handoff = mode == ENV_MODE_TAIL && k.env_steal && p.tail_max >= 1u && p.lane_limit >= 2u;
-    p.gpool = p.handoff && (k.env_grid_steal > 0 || (k.env_grid_steal < 0 && (cap >= GPOOL_MIN_CAP || n_calls > 1u)));
-    p.mode = mode;
-    p.grp = grp;
-    p.erec_shift = erec_shift;
-    p.chunk = chunk;
-    p.bpc = bpc;
-    p.kernel = replay ? std::min(mode, (int)ENV_MODE_COUNTERS) : mode;
-    return p;
+// env_plan with the device's answer to its occupancy queries
+static EnvPlan env_call_plan(const pbn_batch* b, const pbn_envcfg* cfg, const EnvCall& c) {
+    return env_plan(env_plan_in(b, cfg, c), [b](int mode, int grp, uint32_t image_bytes, uint32_t chunk, int* bpc) {
+        return max_blocks_env(b->W, b->net->kind, mode, grp, image_bytes, bpc, chunk);
+    });
 }
 
 // Device pointers of one R6 launch: actions in, outputs, and (replay mode) the recorded draws.
@@ -139,9 +68,9 @@ struct EnvIO {
 };
 
 // The acting half: uploads what the plan needs, zeroes the launch's counters, fills EnvArgs and launches.
-static int env_launch(pbn_batch* b, pbn_envcfg* cfg, const EnvPlan& p, const EnvIO& io, int A, int dedup, int offset,
-                      uint32_t cap, int replay, uint32_t n_calls) {
+static int env_launch(pbn_batch* b, pbn_envcfg* cfg, const EnvCall& c, const EnvPlan& p, const EnvIO& io) {
     if (p.error) return fail(PBN_E_HIP, "occupancy query: %s", hipGetErrorString((hipError_t)p.error));
+    const int replay = c.replay;
     EnvArgs a{};
     a.img = cfg->dev_image.on(b->device, cfg->image.data(), cfg->image.size());
     if (!a.img) return fail(PBN_E_NOMEM, "envcfg upload failed");
@@ -168,7 +97,7 @@ static int env_launch(pbn_batch* b, pbn_envcfg* cfg, const EnvPlan& p, const Env
     a.erec_shift = p.erec_shift;
     a.tail_max = p.tail_max;
     a.lane_limit = p.lane_limit;
-    a.fast = p.mode;
+    a.mode = p.mode;
     a.grp = p.grp;
     a.chunk = p.chunk;
     a.off_gen = p.mode == ENV_MODE_GROUP ? cfg->L.bytes : cfg->L.bytes + p.erec_shift + 8u * (uint32_t)b->W * ENV_BLOCK;
@@ -179,15 +108,15 @@ static int env_launch(pbn_batch* b, pbn_envcfg* cfg, const EnvPlan& p, const Env
     a.env_base = b->env_base;
     a.seed = b->seed;
     a.call_idx = b->r6.calls;
-    a.update_cap = cap;
-    a.A = A;
-    a.offset = offset;
-    a.dedup = dedup ? 1 : 0;
+    a.update_cap = c.cap;
+    a.A = c.A;
+    a.offset = c.offset;
+    a.dedup = c.dedup ? 1 : 0;
     a.horizon = cfg->horizon;
     a.reward_success = cfg->reward_success;
     a.action_cost = cfg->action_cost;
     a.first_tested = cfg->first_tested;
-    a.n_calls = n_calls;
+    a.n_calls = c.n_calls;
     a.draw_off = (const int64_t*)io.draw_off;
     a.draws_i = (const uint32_t*)io.draws_i;
     a.draws_k = (const uint64_t*)io.draws_k;
@@ -222,7 +151,7 @@ static int env_launch(pbn_batch* b, pbn_envcfg* cfg, const EnvPlan& p, const Env
         if (io.obs != b->s_obs.p) b->r6.fault_check = true;  // device path: pbn_sync reads the sticky fault word
     }
     if (int rc = timed_launch(b, "k_env", [&] { return launch_env_multi(b->W, a, replay, p.grid, b->stream); })) return rc;
-    if (!replay) b->r6.calls += n_calls;
+    if (!replay) b->r6.calls += c.n_calls;
     b->r6.last = p;
     return 0;
 }
@@ -296,8 +225,8 @@ static int env_steps_device(pbn_batch* b, const pbn_envcfg* cfg_c, uint32_t n_ca
     if (int rc = check_action_shape(A, offset)) return rc;
     if (n_calls < 1 || n_calls > (1u << 20)) return fail(PBN_E_INVALID, "n_steps=%u outside [1, 2^20]", n_calls);
     SET_DEV(b);
-    const EnvIO io{d_actions, d_obs, d_reward, d_flags, d_n_updates};
-    return env_launch(b, cfg, env_plan(b, cfg, 0, update_cap, n_calls), io, A, dedup, offset, update_cap, 0, n_calls);
+    const EnvCall c{A, dedup, offset, update_cap, 0, n_calls};
+    return env_launch(b, cfg, c, env_call_plan(b, cfg, c), EnvIO{d_actions, d_obs, d_reward, d_flags, d_n_updates});
 }
 
 // The first `words` counters of the last launch's tail hand-off (zeros if it had none).
@@ -358,8 +287,8 @@ int pbn_env_step_multi(pbn_batch* b, const pbn_envcfg* cfg_c, const int32_t* act
     pbn_envcfg* cfg = const_cast<pbn_envcfg*>(cfg_c);
     SET_DEV(b);
     if (int rc = env_host_common(b, cfg, actions, A, offset)) return rc;
-    if (int rc = env_launch(b, cfg, env_plan(b, cfg, 0, update_cap, 1), env_host_io(b), A, dedup, offset, update_cap, 0, 1))
-        return rc;
+    const EnvCall c{A, dedup, offset, update_cap, 0, 1};
+    if (int rc = env_launch(b, cfg, c, env_call_plan(b, cfg, c), env_host_io(b))) return rc;
     return env_host_out(b, obs, reward, flags, n_updates);
 }
 
@@ -407,7 +336,8 @@ int pbn_env_step_multi_replay(pbn_batch* b, const pbn_envcfg* cfg_c, const int32
     io.draw_off = b->s_off.p;
     io.draws_i = b->s_replay_i.p;
     io.draws_k = b->s_replay_k.p;
-    if (int rc = env_launch(b, cfg, env_plan(b, cfg, 1, 0xFFFFFFFFu, 1), io, A, dedup, offset, 0xFFFFFFFFu, 1, 1)) return rc;
+    const EnvCall c{A, dedup, offset, REPLAY_NO_CAP, 1, 1};
+    if (int rc = env_launch(b, cfg, c, env_call_plan(b, cfg, c), io)) return rc;
     return env_host_out(b, obs, reward, flags, n_updates);
 }
 

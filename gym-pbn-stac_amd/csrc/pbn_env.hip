@@ -14,6 +14,7 @@
 
 #include "pbn_device.hpp"
 #include "pbn_env_device.hpp"
+#include "pbn_env_plan.hpp"
 #include "pbn_env_words.hpp"
 #include "pbn_launch.hpp"
 #include "pbn_params.hpp"
@@ -1585,43 +1586,35 @@ __global__ __launch_bounds__(ENV_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
 
 // ------------------------------------------------------------------ dispatch
 template <int KIND>
-static void* env_fn_w(int W, int replay, int fast, int grp) {
-    if (fast == ENV_MODE_GROUP) {
+static void* env_fn_w(int W, int replay, int mode, int grp) {
+    if (mode == ENV_MODE_GROUP) {
         if (KIND != KIND_PREDICTOR_MIX || replay) return nullptr;
         return env_grp_kernel(W, grp);
     }
     return by_words<8>(W, [=](auto w) {
-        if (fast == ENV_MODE_COOP && KIND == KIND_PREDICTOR_MIX && !replay)
+        if (mode == ENV_MODE_COOP && KIND == KIND_PREDICTOR_MIX && !replay)
             return (void*)k_env<w, KIND_PREDICTOR_MIX, 0, ENV_MODE_COOP>;
-        if (fast == ENV_MODE_TAIL && KIND == KIND_PREDICTOR_MIX && !replay)
+        if (mode == ENV_MODE_TAIL && KIND == KIND_PREDICTOR_MIX && !replay)
             return (void*)k_env<w, KIND_PREDICTOR_MIX, 0, ENV_MODE_TAIL>;
-        if (fast) return replay ? (void*)k_env<w, KIND, 1, ENV_MODE_COUNTERS> : (void*)k_env<w, KIND, 0, ENV_MODE_COUNTERS>;
+        if (mode) return replay ? (void*)k_env<w, KIND, 1, ENV_MODE_COUNTERS> : (void*)k_env<w, KIND, 0, ENV_MODE_COUNTERS>;
         return replay ? (void*)k_env<w, KIND, 1, ENV_MODE_CUBES> : (void*)k_env<w, KIND, 0, ENV_MODE_CUBES>;
     });
 }
 
-static void* env_kernel(int W, int kind, int replay, int fast, int grp) {
-    return kind == KIND_PREDICTOR_MIX ? env_fn_w<KIND_PREDICTOR_MIX>(W, replay, fast, grp)
-                                      : env_fn_w<KIND_PROB_TABLE>(W, replay, fast, grp);
+static void* env_kernel(int W, int kind, int replay, int mode, int grp) {
+    return kind == KIND_PREDICTOR_MIX ? env_fn_w<KIND_PREDICTOR_MIX>(W, replay, mode, grp)
+                                      : env_fn_w<KIND_PROB_TABLE>(W, replay, mode, grp);
 }
 
-uint32_t env_lds_bytes(int W, uint32_t image_bytes, int fast, int grp, uint32_t chunk) {
-    if (fast == ENV_MODE_GROUP) return image_bytes + 8u * (uint32_t)W * (BLOCK / (uint32_t)grp);  // one row per group
-    const uint32_t planes = image_bytes + 8u * (uint32_t)W * ENV_BLOCK;
-    // ENV_MODE_TAIL: 16 B of workgroup hand-off control (WgCtl) after the per-wave draw buffers
-    const bool coop = fast == ENV_MODE_COOP || fast == ENV_MODE_TAIL;
-    return coop ? planes + (ENV_BLOCK / 64) * env_gen_wave_bytes(chunk) + (fast == ENV_MODE_TAIL ? 16u : 0u) : planes;
-}
-
+// a replay launch's mode is ENV_MODE_CUBES or _COUNTERS: env_plan (pbn_env_plan.hpp) gives it no other
 int launch_env_multi(int W, const EnvArgs& a, int replay, int grid, void* stream) {
     EnvArgs c = a;
-    return launch(env_kernel(W, a.L.kind, replay, a.fast, a.grp), grid, env_block(a.fast),
-                  env_lds_bytes(W, a.L.bytes + a.erec_shift, replay ? std::min(a.fast, (int)ENV_MODE_COUNTERS) : a.fast, a.grp, a.chunk),
-                  stream, &c);
+    return launch(env_kernel(W, a.L.kind, replay, a.mode, a.grp), grid, env_block(a.mode),
+                  env_lds_bytes(W, a.L.bytes + a.erec_shift, a.mode, a.grp, a.chunk), stream, &c);
 }
 
-int max_blocks_env(int W, int kind, int fast, int grp, uint32_t lds_bytes, int* blocks_per_cu, uint32_t chunk) {
-    return occupancy(env_kernel(W, kind, 0, fast, grp), env_block(fast), env_lds_bytes(W, lds_bytes, fast, grp, chunk),
+int max_blocks_env(int W, int kind, int mode, int grp, uint32_t lds_bytes, int* blocks_per_cu, uint32_t chunk) {
+    return occupancy(env_kernel(W, kind, 0, mode, grp), env_block(mode), env_lds_bytes(W, lds_bytes, mode, grp, chunk),
                      blocks_per_cu);
 }
 

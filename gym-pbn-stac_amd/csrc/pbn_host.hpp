@@ -18,6 +18,7 @@
 
 #include "../../include/pbn_abi.h"
 #include "pbn_params.hpp"
+#include "pbn_env_plan.hpp"
 #include "pbn_step_plan.hpp"
 
 using namespace pbn;
@@ -58,7 +59,7 @@ struct pbn_envcfg {
     std::vector<uint8_t> image;  // net image + cubes [H][2][W] + target [2][W]
     NetLayout L{};
     uint32_t off_cubes = 0, off_target = 0, off_ndelta = 0;
-    int fast = 0;
+    bool counters_ok = false;  // <= 8 cubes, each caring about <= 255 nodes: the byte counters apply (ENV_MODE_COUNTERS)
     std::vector<uint64_t> reset;  // care [H_reset][W], then value [H_reset][W]
     int32_t horizon = 100, reward_success = 1000, action_cost = 1, first_tested = 0;
     std::mutex mu;                   // guards gen_image's construction
@@ -159,15 +160,7 @@ struct Knobs {
     int step_graph = -1;           // PBNSIM_STEP_GRAPH=0/1 forces step mode without / with HIP graphs, -1 = by size
     int step_chains = 0;           // PBNSIM_STEP_CHAINS: 1 / 2 / 4 launch chains of pbn_step, 0 = by size
     int roll_group = -1;           // PBNSIM_ROLL_GROUP: lanes per env of the rollout kernel, -1 = by size
-    bool env_no_gen = false;  // PBNSIM_ENV_NO_GEN: no cooperative draw generation
-    int env_group = 0;        // PBNSIM_ENV_GROUP: lanes per env (1 = lane mode), 0 = by batch size
-    int env_bpc = 0;          // PBNSIM_ENV_BPC: cap on resident workgroups per CU, 0 = none
-    int env_chunk = 0;        // PBNSIM_ENV_CHUNK: draw-round chunk 32 / 48 of the cooperative-draw kernels, 0 = auto
-    int env_grid_cap = 0;     // PBNSIM_ENV_GRID: the R6 kernel's workgroups (tests: lane refill, hand-offs), 0 = by size
-    int env_tail = -1;        // PBNSIM_ENV_TAIL: the R6 kernel's tail-mode threshold (live envs per wave), -1 = default
-    int env_lane_limit = 0;   // PBNSIM_ENV_LANES: lanes per wave taking envs in the tail-mode kernel, 0 = auto
-    bool env_steal = true;    // PBNSIM_ENV_STEAL=0: no hand-off of tail envs between a workgroup's waves (k_env, ENV_MODE_TAIL)
-    bool env_kernel_image = false;  // PBNSIM_ENV_KERNEL_IMAGE=1: k_env builds its LDS image (no host-built image)
+    EnvKnobs env;             // PBNSIM_ENV_*: what env_plan reads (pbn_env_plan.hpp)
     int env_helpers = 3;      // PBNSIM_ENV_HELPERS: at most this many tail helpers per session (0-3; 0 = off)
     // PBNSIM_ENV_GRID_STEAL: grid-wide hand-off of tail envs (k_env, ENV_MODE_TAIL): 1 on, 0 off, unset = fused launches
     // and update caps from GPOOL_MIN_CAP (below it one env step's loops are too short to repay the waiting
@@ -182,22 +175,6 @@ struct Knobs {
     int ssd_shared = -1;      // PBNSIM_SSD_SHARED: 0 = one wave per env, 4 / 8 = that many, 1 = the default
                               // count, -1 = by size
     bool mt_lane_walk = false;  // PBNSIM_MT_LANES=1: MT-mode steps of predictor-mix networks on k_mt_step
-};
-
-// What env_plan (pbn_abi_env.cpp) decides for one R6 launch; the batch keeps the last launched one.
-struct EnvPlan {
-    int mode = -1;            // EnvArgs::fast, an EnvMode (pbn_params.hpp)
-    int grp = 0;              // lanes per env
-    uint32_t erec_shift = 0;  // LDS bytes the 16-B env records add (ENV_MODE_COOP / _TAIL)
-    uint32_t chunk = 0;       // draw-round chunk (ENV_MODE_COOP / _TAIL)
-    int bpc = 1;              // resident workgroups per CU
-    uint32_t lane_limit = 0, tail_max = 0;
-    int grid = 0;             // workgroups
-    bool host_image = false;  // the kernel stages the host-built image (env_gen_image)
-    bool handoff = false;     // tail hand-off between a workgroup's waves
-    bool gpool = false;       // grid-wide hand-off (grid pool)
-    int kernel = -1;          // pbn_batch_info.env_kernel
-    int error = 0;            // hipError_t of a failed occupancy query: no launch
 };
 
 struct pbn_batch {
@@ -301,12 +278,7 @@ struct pbn_batch {
         if (own_stream) (void)hipStreamDestroy(own_stream);
     }
 
-    int grid_for(uint64_t items, int bpc, int block = BLOCK) const {
-        uint64_t need = (items + block - 1) / block;
-        uint64_t cap = (uint64_t)n_cu * (uint64_t)bpc;
-        uint64_t g = std::min<uint64_t>(need, cap);
-        return (int)std::max<uint64_t>(g, 1);
-    }
+    int grid_for(uint64_t items, int bpc, int block = BLOCK) const { return resident_grid(items, n_cu, bpc, block); }
     int grid_all(uint64_t items) const { return (int)std::max<uint64_t>((items + BLOCK - 1) / BLOCK, 1); }
     int ev_new_pair() {
         hipEvent_t a, b;

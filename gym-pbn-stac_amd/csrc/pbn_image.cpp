@@ -214,7 +214,7 @@ int build_envcfg_image(const pbn_net& net, const pbn_envcfg_desc* d, pbn_envcfg*
         for (int k = 0; k < W; k++) pc += __builtin_popcountll(d->cube_care[(size_t)h * W + k]);
         max_care = std::max(max_care, pc);
     }
-    c->fast = (c->H <= 8 && max_care <= 255) ? 1 : 0;
+    c->counters_ok = c->H <= 8 && max_care <= 255;
     uint32_t* nd = reinterpret_cast<uint32_t*>(c->image.data() + c->off_ndelta);
     for (int i = 0; i < net.N; i++) {
         uint32_t plus[2] = {0, 0}, minus[2] = {0, 0};

@@ -16,7 +16,7 @@ enum {
     STREAM_SYNC_PERT = 8
 };
 enum { STORE_FULL = 0, STORE_DIRTY = 1 };
-// R6 env-step modes: EnvArgs::fast, EnvPlan::mode and k_env's template parameter
+// R6 env-step modes: EnvArgs::mode, EnvPlan::mode and k_env's template parameter
 enum EnvMode {
     ENV_MODE_CUBES = 0,     // the state matched against every cube after a change
     ENV_MODE_COUNTERS = 1,  // <= 8 cubes, each caring about <= 255 nodes: packed byte counters
@@ -158,7 +158,7 @@ struct EnvArgs {
     uint32_t off_ndelta;     // per node: uint2 packed mismatch-counter deltas (fast attractor test)
     unsigned long long* counter;  // work-queue head (zeroed per launch)
     int32_t n_cubes;
-    int32_t fast;            // the kernel's mode: an EnvMode (above)
+    int32_t mode;            // the kernel's mode: an EnvMode (above)
     uint32_t off_gen;        // ENV_MODE_COOP / _TAIL: per-wave draw buffers (ENV_GEN_WAVE_BYTES each);
                              // ENV_MODE_GROUP: per-group env rows (2W dwords per group of grp lanes)
     uint64_t B, env_base, seed;
@@ -380,9 +380,9 @@ constexpr uint32_t ENV_CHUNK_SMALL = 32, ENV_CHUNK_LARGE = 48;
 // a wave's draw buffer: the draw table [chunk][64] u16, 64 B (the hand-off flag in tail mode), the
 // shared rounds' counter table [64] uint4 by rank (the hand-off box in tail mode)
 constexpr uint32_t env_gen_wave_bytes(uint32_t chunk) { return chunk * 64u * 2u + 64u + 64u * 16u; }
-int max_blocks_env(int W, int kind, int fast, int grp, uint32_t lds_bytes, int* blocks_per_cu, uint32_t chunk = ENV_CHUNK_LARGE);
-uint32_t env_lds_bytes(int W, uint32_t image_bytes, int fast, int grp, uint32_t chunk = ENV_CHUNK_LARGE);
-inline int env_block(int fast) { return fast == ENV_MODE_GROUP ? BLOCK : ENV_BLOCK; }  // threads per workgroup of the R6 kernel
+// lds_bytes: the image's; the workgroup's LDS is env_lds_bytes of it (pbn_env_plan.hpp)
+int max_blocks_env(int W, int kind, int mode, int grp, uint32_t lds_bytes, int* blocks_per_cu, uint32_t chunk = ENV_CHUNK_LARGE);
+inline int env_block(int mode) { return mode == ENV_MODE_GROUP ? BLOCK : ENV_BLOCK; }  // threads per workgroup of the R6 kernel
 int launch_mt_seed(int W, const MTArgs& a, int grid, void* stream);
 int launch_mt_step(int W, const MTArgs& a, int n_cu, void* stream);  // grid from the kernel's occupancy
 uint32_t ssd_block(const SSDArgs& a);

@@ -148,7 +148,7 @@ static void check_envcfg(const pbn_net& net, int H, int H_reset, int care_nodes,
     const int W = net.W;
     pbn_envcfg c;
     CHECK(build_envcfg_image(net, &e.desc, &c) == 0);
-    CHECK(c.W == W && c.H == H && c.H_reset == H_reset && c.fast == want_fast);
+    CHECK(c.W == W && c.H == H && c.H_reset == H_reset && c.counters_ok == want_fast);
     CHECK(c.off_cubes == net.L.bytes && c.off_cubes % 16 == 0 && c.off_target % 16 == 0 && c.off_ndelta % 16 == 0);
     CHECK(c.off_target >= c.off_cubes + 16u * W * H && c.off_ndelta >= c.off_target + 16u * W);
     CHECK(c.L.bytes == c.image.size() && c.L.bytes >= c.off_ndelta + 8u * net.N && c.L.plane_off == c.L.bytes);
@@ -164,7 +164,7 @@ static void check_envcfg(const pbn_net& net, int H, int H_reset, int care_nodes,
         CHECK(load<uint64_t>(im + c.off_target + 8 * (size_t)k) == e.tcare[k]);
         CHECK(load<uint64_t>(im + c.off_target + 8 * (size_t)(W + k)) == (e.tvalue[k] & e.tcare[k]));
     }
-    if (c.fast)  // node i going 0 -> 1 moves the packed counters by its delta, from any state
+    if (c.counters_ok)  // node i going 0 -> 1 moves the packed counters by its delta, from any state
         for (int i = 0; i < net.N; i++) {
             std::vector<uint64_t> x(W);
             for (auto& w : x) w = rnd();
@@ -190,7 +190,7 @@ static void check_gen_image(const PredNet& p, const pbn_net& net, int H) {
     CHECK(build_envcfg_image(net, &e.desc, &c) == 0);
     const Thr32 X = thr32_layout(c.L);
     const uint32_t N = (uint32_t)net.N;
-    const uint32_t erec_shift = c.L.off_rec + 16u * N * X.rs - c.off_cubes;  // as env_plan (pbn_abi_env.cpp) sets it
+    const uint32_t erec_shift = c.L.off_rec + 16u * N * X.rs - c.off_cubes;  // as env_plan (pbn_env_plan.hpp) sets it
     const std::vector<uint8_t> g = env_gen_image(&c, erec_shift);
     CHECK(g.size() == (size_t)c.L.bytes + erec_shift);
     CHECK(memcmp(g.data(), net.image.data() + net.L.bytes, 4 * (size_t)N * X.tp4) == 0);

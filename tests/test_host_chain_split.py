@@ -1,4 +1,5 @@
-"""The slice rule of step mode's launch chains (csrc/pbn_chain_split.hpp) under host sanitizers, on the CPU.
+"""The HIP-free decision headers of the host side (csrc/pbn_chain_split.hpp, pbn_step_plan.hpp, pbn_env_plan.hpp) under
+host sanitizers, on the CPU. First the slice rule of step mode's launch chains:
 
 ``make chainsplitcheck`` compiles tests/host/chain_split_check.cpp (no HIP header, no library, no GPU) with
 ASan + UBSan and runs it: for every batch size up to 5,000, 1 / 2 / 4 chains and both step block sizes (and
@@ -32,3 +33,16 @@ def test_step_plan_is_clean_under_asan_and_ubsan():
                        text=True)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "step_plan_check ok" in r.stdout
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ is not installed")
+def test_env_plan_is_clean_under_asan_and_ubsan():
+    """``make envplancheck``: tests/host/env_plan_check.cpp on csrc/pbn_env_plan.hpp, the same way. Every field of
+    the R6 launch plan, and the occupancy queries it makes in their order, against a restatement of the rule as the
+    host files held it, over the layouts of the Bittner networks and tt200 and four synthetic ones, 1 to 12 cubes,
+    batch sizes either side of every threshold, per-step and fused calls, replay, and every PBNSIM_ENV_* knob forced;
+    no class of plan (each kernel mode, chunk, lane limit, hand-off, grid pool, failed query) is left empty."""
+    r = subprocess.run(["make", "-C", str(ROOT / "gym-pbn-stac_amd"), "envplancheck"], capture_output=True,
+                       text=True)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "env_plan_check ok" in r.stdout

@@ -547,3 +547,52 @@ def test_tail_handoff_forced_happens_and_matches_oracle(G, oracle_mod, monkeypat
         st, ns = ref["state"], ref["n_steps"]
     assert np.array_equal(b.get_state(), st) and np.array_equal(b.get_n_steps(), ns)
     b.close()
+
+
+def test_replay_then_philox_on_one_batch_reports_each_plan(G, oracle_mod):
+    """What ``info()`` reports follows the launch plan (csrc/pbn_env_plan.hpp) through both draw sources on one
+    batch: 64 Bittner-28 envs under the r6 fixture's 4 cubes. A replay step (env e replays fixture record e: its
+    state before the step, its actions, its recorded draws) runs the byte-counter kernel -- a replay launch's
+    mode never leaves {0, 1} -- in lane mode with no draw-round chunk; the Philox step that follows runs the
+    tail kernel. Both equal the oracle on every env and field, and the replay step equals the fixture."""
+    z = golden("r6_bittner28.npz")
+    net = load_network("bittner28")
+    gnet = G.Net(net)
+    cfg = G.EnvConfig(gnet, cubes_to_attractors(z, net.n_nodes), horizon=int(z["horizon"]))
+    cfgd = r6_config(z)
+    assert cfg.cube_care.shape[0] <= 4
+    B, seed, base = 64, 0x5EED, 4242
+    rec = np.nonzero(z["is_list"] == 0)[0][:B]  # one dedup setting per launch
+    assert len(rec) == B
+    t0 = z["t"][rec] == 0
+    st = np.where(t0[:, None], z["reset_state"][rec], z["state_after"][rec - 1])
+    ns = np.where(t0, 0, z["n_steps"][rec - 1]).astype(np.int64)
+    lo, hi = z["draw_offsets"][rec], z["draw_offsets"][rec + 1]
+    rep = (np.concatenate([[0], np.cumsum(hi - lo)]), np.concatenate([z["draws_i"][a:e] for a, e in zip(lo, hi)]),
+           np.concatenate([z["draws_k"][a:e] for a, e in zip(lo, hi)]))
+    o = oracle_mod.Oracle(net)
+    b = G.PBNBatch(gnet, B, seed=seed, env_id_base=base)
+    b.set_state(st)
+    b.set_n_steps(ns)
+
+    def same(got, ref):
+        obs, rew, flags, nup = got
+        assert np.array_equal(nup, ref["n_updates"])
+        assert np.array_equal(obs, ref["obs"]) and np.array_equal(rew, ref["reward"])
+        assert np.array_equal(flags, ref["flags"])
+        assert np.array_equal(b.get_state(), ref["state"]) and np.array_equal(b.get_n_steps(), ref["n_steps"])
+
+    got = b.env_step_multi(cfg, z["actions"][rec], replay=rep)
+    info = b.info()
+    assert info["env_kernel"] == 1 and info["env_lanes"] == 1 and info["env_chunk"] == 0
+    ref = o.env_step_multi(cfgd, st, ns, z["actions"][rec], replay=rep)
+    same(got, ref)
+    assert np.array_equal(got[0], z["obs"][rec]) and np.array_equal(ref["state"], z["state_after"][rec])
+    assert np.array_equal(got[3], hi - lo) and np.array_equal(ref["n_steps"], z["n_steps"][rec])
+    assert info["env_call_count"] == 0  # a replay step takes no Philox call index
+    acts = _actions(np.random.default_rng(5), (B, 4), net.n_nodes)
+    got = b.env_step_multi(cfg, acts, update_cap=CAP)
+    assert b.info()["env_kernel"] == 4
+    same(got, o.env_step_multi(cfgd, ref["state"], ref["n_steps"], acts, seed=seed, env_base=base, call_idx=0,
+                               update_cap=CAP))
+    b.close()
