@@ -1,21 +1,19 @@
 // pbn_abi_reach.cpp -- attractor discovery (pbn_reach.hip): the pbn_reach_* entry points.
 #include "pbn_host.hpp"
 
-extern "C" {
-
-int pbn_reach_create(const pbn_net* net_c, int device, uint64_t max_states, pbn_reach** out) {
-    CHECK_NN(net_c, "net");
-    CHECK_NN(out, "out");
-    *out = nullptr;
-    pbn_net* net = const_cast<pbn_net*>(net_c);
-    if (net->kind != PBN_KIND_PREDICTOR_MIX)
-        return fail(PBN_E_UNSUPPORTED, "attractor discovery covers predictor-mix networks (truth-table networks: stg.py)");
+// The set of one network on one device; graph: TABLE_GRAPH_NONE for predictor mix, else the table graph.
+static int reach_create(pbn_net* net, int device, uint64_t max_states, int graph, pbn_reach** out) {
     if (max_states < 1 || max_states > PBN_REACH_MAX_STATES)
         return fail(PBN_E_INVALID, "max_states=%llu outside [1, %llu]", (unsigned long long)max_states,
                     (unsigned long long)PBN_REACH_MAX_STATES);
+    // the edge-rule kernels stage the whole image: one that does not fit is refused here, never launched
+    if (net->L.bytes > REACH_LDS_MAX)
+        return fail(PBN_E_UNSUPPORTED, "network image (%u B) exceeds the %u B of LDS the attractor kernels stage it in",
+                    net->L.bytes, REACH_LDS_MAX);
     if (int rc = open_device(device)) return rc;
     pbn_reach* r = new pbn_reach;
     r->net = net;
+    r->graph = graph;
     r->device = device;
     r->W = net->W;
     r->max_states = (uint32_t)max_states;
@@ -51,6 +49,31 @@ int pbn_reach_create(const pbn_net* net_c, int device, uint64_t max_states, pbn_
     return 0;
 }
 
+extern "C" {
+
+int pbn_reach_create(const pbn_net* net_c, int device, uint64_t max_states, pbn_reach** out) {
+    CHECK_NN(net_c, "net");
+    CHECK_NN(out, "out");
+    *out = nullptr;
+    pbn_net* net = const_cast<pbn_net*>(net_c);
+    if (net->kind != PBN_KIND_PREDICTOR_MIX)
+        return fail(PBN_E_UNSUPPORTED, "attractor discovery covers predictor-mix networks here (truth-table networks "
+                                       "have two support graphs: pbn_reach_create_table takes the choice)");
+    return reach_create(net, device, max_states, TABLE_GRAPH_NONE, out);
+}
+
+int pbn_reach_create_table(const pbn_net* net_c, int device, uint64_t max_states, int32_t graph, pbn_reach** out) {
+    CHECK_NN(net_c, "net");
+    CHECK_NN(out, "out");
+    *out = nullptr;
+    pbn_net* net = const_cast<pbn_net*>(net_c);
+    if (net->kind != PBN_KIND_PROB_TABLE)
+        return fail(PBN_E_INVALID, "pbn_reach_create_table takes a truth-table network (predictor mix: pbn_reach_create)");
+    if (graph != PBN_TABLE_GRAPH_STG && graph != PBN_TABLE_GRAPH_STEP)
+        return fail(PBN_E_INVALID, "graph=%d is neither PBN_TABLE_GRAPH_STG nor PBN_TABLE_GRAPH_STEP", (int)graph);
+    return reach_create(net, device, max_states, graph, out);
+}
+
 void pbn_reach_destroy(pbn_reach* r) {
     if (!r) return;
     (void)hipSetDevice(r->device);
@@ -70,6 +93,8 @@ int pbn_reach_get_info(const pbn_reach* r, pbn_reach_info* info) {
     info->key_capacity = r->key_cap;
     info->n_states = r->count;
     info->n_entries = r->n_keys;
+    info->kind = r->net->kind;
+    info->table_graph = r->graph;
     return 0;
 }
 

@@ -20,6 +20,7 @@
 #include "pbn_params.hpp"
 #include "pbn_env_plan.hpp"
 #include "pbn_step_plan.hpp"
+#include "pbn_reach_rule.hpp"
 
 using namespace pbn;
 
@@ -74,6 +75,7 @@ PBN_HIDDEN int build_table_image(const pbn_net_desc* d, pbn_net* n);
 PBN_HIDDEN int build_envcfg_image(const pbn_net& net, const pbn_envcfg_desc* d, pbn_envcfg* c);
 PBN_HIDDEN std::vector<uint8_t> env_gen_image(const pbn_envcfg* cfg, uint32_t erec_shift);
 PBN_HIDDEN uint64_t net_select_u32(const pbn_net* n, int32_t node, uint32_t a);
+PBN_HIDDEN void net_unstable(const pbn_net* n, int graph, const uint64_t* states, uint64_t n_states, uint64_t* masks);
 
 #ifndef PBN_HOST_NO_HIP
 #define HIP_TRY(expr)                                                                              \
@@ -332,6 +334,7 @@ PBN_HIDDEN int run_init(pbn_batch* b, const pbn_envcfg* cfg, const void* d_mask,
 struct pbn_reach {
     pbn_net* net = nullptr;
     int device = 0, W = 0;
+    int graph = TABLE_GRAPH_NONE;  // truth-table networks: PBN_TABLE_GRAPH_STG / _STEP (pbn_reach_create_table)
     hipStream_t stream = nullptr;
     const void* d_image = nullptr;
     uint32_t max_states = 0, key_cap = 0, tcap = 0, fcap = 0;
@@ -353,6 +356,7 @@ struct pbn_reach {
         ReachArgs a{};
         a.img = d_image;
         a.L = net->L;
+        a.first_node = table_graph_first_node(graph);
         a.keys = (uint64_t*)keys.p;
         a.mark = (uint32_t*)mark.p;
         a.table = (unsigned long long*)table.p;

@@ -174,6 +174,30 @@ uint64_t net_select_u32(const pbn_net* n, int32_t node, uint32_t a) {
     return load64(cm + X.rec_off + 8 * ((size_t)node * X.rs + j));
 }
 
+// The support graphs' edge rule (pbn_reach_rule.hpp, the definition k_unstable evaluates) on the host copy of
+// the u64 image: masks [S][W], bit i set iff node i can flip at states [S][W]. graph: a truth-table network's
+// PBN_TABLE_GRAPH_*; predictor mix has one graph.
+static_assert((int)PBN_TABLE_GRAPH_STG == (int)TABLE_GRAPH_STG && (int)PBN_TABLE_GRAPH_STEP == (int)TABLE_GRAPH_STEP,
+              "the ABI's graph codes are the rule header's");
+
+void net_unstable(const pbn_net* n, int graph, const uint64_t* states, uint64_t n_states, uint64_t* masks) {
+    const uint32_t N = (uint32_t)n->L.n_nodes, W = (uint32_t)n->W;
+    const bool table = n->L.kind == KIND_PROB_TABLE;
+    const uint32_t first = table ? table_graph_first_node(graph) : 0u;
+    const uint8_t* im = n->image.data();
+    for (uint64_t e = 0; e < n_states; e++) {
+        const uint64_t* s = states + e * W;
+        uint64_t* m = masks + e * W;
+        auto bit = [s](uint32_t j) { return (uint32_t)(s[j >> 6] >> (j & 63u)) & 1u; };
+        for (uint32_t k = 0; k < W; k++) m[k] = 0;
+        for (uint32_t i = 0; i < N; i++) {
+            const uint32_t f = table ? can_flip<KIND_PROB_TABLE>(bit, i, first, im, n->L)
+                                     : can_flip<KIND_PREDICTOR_MIX>(bit, i, first, im, n->L);
+            m[i >> 6] |= (uint64_t)f << (i & 63u);
+        }
+    }
+}
+
 // The env config's image: the network's u64 image, the attractor cubes, the target and the per-node
 // counter deltas; `c` also takes the reset cubes and the scalars of `d`.
 int build_envcfg_image(const pbn_net& net, const pbn_envcfg_desc* d, pbn_envcfg* c) {

@@ -318,10 +318,14 @@ constexpr uint32_t REACH_NONE = 0xFFFFFFFFu;
 constexpr uint32_t REACH_DEAD = 0x80000000u;     // mark of a dead entry (epochs stay below it)
 constexpr uint32_t REACH_CHUNK = 16384;          // frontier entries per launch (short launches; a level takes several)
 constexpr uint32_t REACH_MAX_GRID = 2048;        // workgroups per launch (4 waves each; a wave walks its entries)
+// the edge-rule kernels stage the whole network image as dynamic LDS and ask for no more than a launch gets
+// without opting in; a network whose image is larger has no pbn_reach (TT-200: 28.8 KiB)
+constexpr uint32_t REACH_LDS_MAX = 64u * 1024u;
 
 struct ReachArgs {
-    const void* img;             // network image (predictor mix)
+    const void* img;             // network image (the u64 image of either kind; L.kind selects the edge rule)
     NetLayout L;
+    uint32_t first_node;         // lowest node that may move: 0, or 1 for a truth-table network's "step" graph
     uint64_t* keys;
     uint32_t* mark;              // [key_cap] epoch of the last mark_backward that reached the entry, or REACH_DEAD
     unsigned long long* table;

@@ -1,12 +1,16 @@
-// pbn_reach.hip -- attractor discovery on the support graph of a predictor-mix network.
+// pbn_reach.hip -- attractor discovery on the support graph of a network.
 //
-// The support graph has an edge x -> x ^ (1 << i) iff some live predictor of node i outputs 1 - x_i
-// at x (the support of the reference's getNextStates, base.py:221-242: it keeps an edge when prob > 0;
+// Predictor mix: the support graph has an edge x -> x ^ (1 << i) iff some live predictor of node i outputs
+// 1 - x_i at x (the support of the reference's getNextStates, base.py:221-242: it keeps an edge when prob > 0;
 // base.py:398-399 findAttractors takes the terminal strongly connected components). A predictor is live
 // iff its selection interval on the 53-bit grid is non-empty, so the rule is defined on the 53-bit
 // thresholds of the network image, not on the 32-bit grid of the Philox stream.
+// Truth tables: the edge exists iff the table entry of node i at x lets it leave x_i (threshold > 0 from 0,
+// < 2^53 from 1), over nodes first_node .. N-1: 0 for the graph of PBN._compute_next_states, 1 for the graph
+// PBN.step walks. Both rules are defined once, for the kernels and the host, in pbn_reach_rule.hpp; the
+// kernels that evaluate them are templated on the network kind.
 //
-// Mapping: one wave per state, lanes over nodes. All the work of a state (N predictor-row reads, up to N
+// Mapping: one wave per state, lanes over nodes. All the work of a state (N table-row reads, up to N
 // set operations) is then one wave's, the state words are wave-uniform registers, and the set operations
 // of a wave hit N different slots; one lane per state would serialise N dependent hash probes per lane.
 //
@@ -14,6 +18,7 @@
 // size, and a full table / key array / max_states only raises the overflow word.
 #include "pbn_device.hpp"
 #include "pbn_launch.hpp"
+#include "pbn_reach_rule.hpp"
 
 namespace pbn {
 
@@ -31,30 +36,11 @@ __device__ __forceinline__ unsigned long long ld64(const unsigned long long* p) 
 __device__ __forceinline__ uint32_t ld32(const uint32_t* p) { return __hip_atomic_load(p, RLX, AGENT); }
 __device__ __forceinline__ void raise_flag(uint32_t* p) { __hip_atomic_store(p, 1u, RLX, AGENT); }
 
-// 1 iff node i can flip at state s: some live predictor of node i outputs 1 - s_i.
-// Image (build_predictor_image): thr [N][tp] u64, the thresholds of the last predictor and of the padding
-// UINT64_MAX -- clamped to 2^53 here, which is "the last threshold taken as 2^53" and makes every slot
-// past the node's predictors an empty interval; rec [N][pmax] in0 | in1<<16 | in2<<32 | tt<<48.
-template <int W>
-__device__ __forceinline__ uint32_t can_flip(const uint64_t (&s)[W], uint32_t i, const uint8_t* tbl,
-                                             const NetLayout& L) {
-    const uint64_t* thr = reinterpret_cast<const uint64_t*>(tbl + L.off_thr) + i * L.tp;
-    const uint64_t* rec = reinterpret_cast<const uint64_t*>(tbl + L.off_rec) + i * L.pmax;
-    const uint32_t xi = getbit<W>(s, i);
-    uint64_t prev = 0;
-    uint32_t flip = 0;
-    for (uint32_t q = 0; q < L.pmax; ++q) {
-        uint64_t t = q < L.tp ? thr[q] : ~0ull;
-        t = t > (1ull << 53) ? (1ull << 53) : t;
-        const bool live = t > prev;
-        prev = t > prev ? t : prev;
-        const uint64_t r = rec[q];
-        const uint32_t p = (getbit<W>(s, (uint32_t)r & 0xFFFFu) << 3) | (getbit<W>(s, (uint32_t)(r >> 16) & 0xFFFFu) << 2) |
-                           (getbit<W>(s, (uint32_t)(r >> 32) & 0xFFFFu) << 1) | xi;
-        const uint32_t y = (uint32_t)(r >> (48 + p)) & 1u;
-        flip |= live ? (y ^ xi) : 0u;
-    }
-    return flip;
+// 1 iff node i can flip at state s (pbn_reach_rule.hpp), the state words read out of registers.
+template <int W, int KIND>
+__device__ __forceinline__ uint32_t can_flip_at(const uint64_t (&s)[W], uint32_t i, const uint8_t* tbl,
+                                                const ReachArgs& a) {
+    return can_flip<KIND>([&](uint32_t j) { return getbit<W>(s, j); }, i, a.first_node, tbl, a.L);
 }
 
 template <int W>
@@ -173,7 +159,7 @@ __device__ __forceinline__ const uint8_t* stage(const ReachArgs& a, uint8_t* lds
 }
 
 // ---- unstable: masks of the nodes that can flip, one wave per state, a ballot per 64 nodes
-template <int W>
+template <int W, int KIND>
 __global__ __launch_bounds__(BLOCK) void k_unstable(ReachArgs a) {
     extern __shared__ __align__(16) uint8_t lds[];
     const uint8_t* tbl = stage(a, lds);
@@ -186,7 +172,7 @@ __global__ __launch_bounds__(BLOCK) void k_unstable(ReachArgs a) {
 #pragma unroll
         for (int k = 0; k < W; ++k) {
             const uint32_t i = 64u * k + lane;
-            const uint64_t m = __ballot(i < N && can_flip<W>(s, i, tbl, a.L));
+            const uint64_t m = __ballot(i < N && can_flip_at<W, KIND>(s, i, tbl, a));
             if (lane == 0) a.out[e * W + k] = m;
         }
     }
@@ -204,7 +190,7 @@ __global__ __launch_bounds__(BLOCK) void k_reach_seed(ReachArgs a) {
 }
 
 // ---- forward expansion of the frontier queue[lo, hi): entries the launch publishes are appended past hi
-template <int W>
+template <int W, int KIND>
 __global__ __launch_bounds__(BLOCK) void k_reach_expand(ReachArgs a) {
     extern __shared__ __align__(16) uint8_t lds[];
     const uint8_t* tbl = stage(a, lds);
@@ -216,7 +202,7 @@ __global__ __launch_bounds__(BLOCK) void k_reach_expand(ReachArgs a) {
 #pragma unroll
         for (int k = 0; k < W; ++k) s[k] = a.keys[(uint64_t)e * W + k];
         for (uint32_t i = lane; i < N; i += 64u) {
-            if (!can_flip<W>(s, i, tbl, a.L)) continue;
+            if (!can_flip_at<W, KIND>(s, i, tbl, a)) continue;
             uint64_t t[W];
 #pragma unroll
             for (int k = 0; k < W; ++k) t[k] = s[k];
@@ -244,8 +230,9 @@ __global__ __launch_bounds__(64) void k_reach_back_start(ReachArgs a) {
 }
 
 // ---- backward marking of the frontier queue[lo, hi): x = y ^ (1 << i) is marked iff it is in the set,
-// unmarked, and node i can flip at x (the edge x -> y). Lookups only.
-template <int W>
+// unmarked, and node i can flip at x (the edge x -> y). Lookups only. A node below first_node has no edge:
+// can_flip_at says so after the lookup, as for any other node that cannot move.
+template <int W, int KIND>
 __global__ __launch_bounds__(BLOCK) void k_reach_back(ReachArgs a) {
     extern __shared__ __align__(16) uint8_t lds[];
     const uint8_t* tbl = stage(a, lds);
@@ -263,7 +250,7 @@ __global__ __launch_bounds__(BLOCK) void k_reach_back(ReachArgs a) {
             flip_bit<W>(x, i);
             const uint32_t j = reach_find<W, false>(a, x);
             if (j == REACH_NONE || ld32(a.mark + j) == a.epoch) continue;
-            if (!can_flip<W>(x, i, tbl, a.L)) continue;
+            if (!can_flip_at<W, KIND>(x, i, tbl, a)) continue;
             if (__hip_atomic_exchange(a.mark + j, a.epoch, RLX, AGENT) != a.epoch) {
                 const uint32_t p = __hip_atomic_fetch_add(a.ctl + REACH_QTAIL, 1u, RLX, AGENT);
                 if (p < a.key_cap) a.queue[p] = j;  // one append per entry: p < live entries <= key_cap
@@ -306,24 +293,29 @@ __global__ __launch_bounds__(BLOCK) void k_reach_hull(ReachArgs a) {
 
 }  // namespace
 
+// The kernels that evaluate the edge rule, by words and network kind.
+#define REACH_BY_KIND(kernel)                                                                                     \
+    (a.L.kind == KIND_PROB_TABLE ? by_words<MAX_WORDS>(W, [](auto w) { return (void*)kernel<w, KIND_PROB_TABLE>; }) \
+                                 : by_words<MAX_WORDS>(W, [](auto w) { return (void*)kernel<w, KIND_PREDICTOR_MIX>; }))
+
 int launch_reach(int W, int which, const ReachArgs& a, int grid, void* stream) {
     ReachArgs c = a;
     void* fn = nullptr;
     int block = BLOCK;
     uint32_t lds = a.L.bytes;
     switch (which) {
-        case REACH_K_UNSTABLE: fn = by_words<MAX_WORDS>(W, [](auto w) { return (void*)k_unstable<w>; }); break;
+        case REACH_K_UNSTABLE: fn = REACH_BY_KIND(k_unstable); break;
         case REACH_K_SEED:
             fn = by_words<MAX_WORDS>(W, [](auto w) { return (void*)k_reach_seed<w>; });
             lds = 0;
             break;
-        case REACH_K_EXPAND: fn = by_words<MAX_WORDS>(W, [](auto w) { return (void*)k_reach_expand<w>; }); break;
+        case REACH_K_EXPAND: fn = REACH_BY_KIND(k_reach_expand); break;
         case REACH_K_BACK_START:
             fn = by_words<MAX_WORDS>(W, [](auto w) { return (void*)k_reach_back_start<w>; });
             lds = 0;
             block = 64;
             break;
-        case REACH_K_BACK: fn = by_words<MAX_WORDS>(W, [](auto w) { return (void*)k_reach_back<w>; }); break;
+        case REACH_K_BACK: fn = REACH_BY_KIND(k_reach_back); break;
         case REACH_K_HULL:
             fn = by_words<MAX_WORDS>(W, [](auto w) { return (void*)k_reach_hull<w>; });
             lds = 0;

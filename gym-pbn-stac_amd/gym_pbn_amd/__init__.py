@@ -30,7 +30,7 @@ def __getattr__(name):
         from . import envs
 
         return getattr(envs, name)
-    if name in ("find_attractors", "AttractorResult", "ReachSet", "cube_cover"):
+    if name in ("find_attractors", "AttractorResult", "ReachSet", "cube_cover", "host_unstable"):
         from . import attractors
 
         return getattr(attractors, name)

@@ -30,6 +30,10 @@ PBN_E_NOMEM = -4
 PBN_E_UNSUPPORTED = -5
 PBN_E_STATE = -6
 
+# truth-table networks: the support graph a state set walks (PBN_TABLE_GRAPH_*)
+TABLE_GRAPH_STG = 1
+TABLE_GRAPH_STEP = 2
+
 FLAG_TERMINATED = 1
 FLAG_TRUNCATED = 2
 FLAG_CAPPED = 4
@@ -83,6 +87,7 @@ class ReachInfo(C.Structure):
         ("n_nodes", C.c_int32), ("n_words", C.c_int32), ("device", C.c_int32), ("complete", C.c_int32),
         ("max_states", C.c_uint64), ("table_slots", C.c_uint64), ("key_capacity", C.c_uint64),
         ("n_states", C.c_uint64), ("n_entries", C.c_uint64),
+        ("kind", C.c_int32), ("table_graph", C.c_int32),
     ]
 
 
@@ -96,6 +101,7 @@ SIGNATURES = {
     "pbn_net_create": (C.c_int, [C.POINTER(NetDesc), _PP]),
     "pbn_net_destroy": (None, [_vp]),
     "pbn_net_select_u32": (C.c_int, [_vp, C.c_int32, C.c_uint32, _u64p]),
+    "pbn_net_unstable": (C.c_int, [_vp, C.c_int32, _u64p, C.c_uint64, _u64p]),
     "pbn_batch_create": (C.c_int, [_vp, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, _PP]),
     "pbn_batch_destroy": (None, [_vp]),
     "pbn_batch_get_info": (C.c_int, [_vp, C.POINTER(BatchInfo)]),
@@ -140,6 +146,7 @@ SIGNATURES = {
     "pbn_env_tail_stats": (C.c_int, [_vp, _u32p]),
     "pbn_env_grid_stats": (C.c_int, [_vp, _u32p]),
     "pbn_reach_create": (C.c_int, [_vp, C.c_int, C.c_uint64, _PP]),
+    "pbn_reach_create_table": (C.c_int, [_vp, C.c_int, C.c_uint64, C.c_int32, _PP]),
     "pbn_reach_destroy": (None, [_vp]),
     "pbn_reach_get_info": (C.c_int, [_vp, C.POINTER(ReachInfo)]),
     "pbn_reach_unstable": (C.c_int, [_vp, _u64p, C.c_uint64, _u64p]),

@@ -1,4 +1,4 @@
-"""Attractor discovery for predictor-mix (Bittner) networks, on the device.
+"""Attractor discovery for predictor-mix (Bittner) and truth-table networks, on the device.
 
 The reference gets ``all_attractors`` from the external ``cabean`` binary
 (``get_attractors_from_cabean.py:39-54``); its own exhaustive route
@@ -15,6 +15,21 @@ live iff its selection interval on the **53-bit grid** is non-empty -- the width
 when ``prob > 0``); it is deliberately *not* defined on the 32-bit grid of the Philox
 choice word, so a predictor narrower than ``2**-32`` still counts.
 
+**Truth-table networks** (``common/pbn.py`` ``PBN``) have two support graphs, and the caller
+names one (``table_graph``). In both, node ``i`` can flip at ``x`` iff its table entry ``p`` at
+``x`` lets it leave ``x_i``: ``p > 0`` from 0, ``p < 1`` from 1 -- evaluated on the 53-bit
+threshold ``T = ceil(p * 2**53)`` as ``T > 0`` / ``T < 2**53``, which is the same test exactly
+(a double ``p > 0`` has ``T >= 1``; a double ``p < 1`` has ``p * 2**53 <= 2**53 - 1``).
+
+* ``"stg"``: every node may move. This is ``PBN._compute_next_states``' async branch
+  (``pbn.py:186-199``), the graph behind ``PBNEnv.compute_attractors`` and
+  :func:`gym_pbn_amd.stg.compute_attractors`: the drop-in ``all_attractors``, without the
+  ``2**N`` enumeration (:mod:`gym_pbn_amd.stg` stops at 22 nodes).
+* ``"step"``: nodes ``1..N-1`` only, the graph ``PBN.step`` walks (``randint(1, N-1)``; ``reset``
+  clears node 0): where the simulation can end up.
+
+The two differ on almost every network, so :class:`ReachSet` has no default between them.
+
 **Attractor.** A terminal strongly connected component of the support graph, the same
 object as ``nx.attracting_components`` on the reference's STG.
 
@@ -23,9 +38,6 @@ exactly an attractor: its closure was enumerated to the fixed point and every st
 it reaches every other. *Coverage* depends on the seeds: an attractor no seed reaches is
 not reported. A closure that does not fit ``max_states`` is reported under
 ``incomplete`` with the hull cube of the states seen -- never guessed at.
-
-Truth-table networks are not covered (``PBN_E_UNSUPPORTED``); :mod:`gym_pbn_amd.stg` is
-their route.
 """
 
 from __future__ import annotations
@@ -38,18 +50,35 @@ import numpy as np
 
 from . import _lib as L
 from .batch import Net, PBNBatch, unpack_bits
+from .network import KIND_PROB_TABLE
 
 MAX_ENV_CUBES = 4096  # pbn_envcfg_create's limit on cubes
+MAX_ENV_STATES = 1 << 16  # PBNEnv / VecPBNEnv keep their attractors as Python sets of state tuples
+TABLE_GRAPHS = {"stg": L.TABLE_GRAPH_STG, "step": L.TABLE_GRAPH_STEP}
 
 
 class ReachSet:
-    """The device state set of one network (``pbn_reach_*``): closure, backward marks, read-back."""
+    """The device state set of one network (``pbn_reach_*``): closure, backward marks, read-back.
 
-    def __init__(self, net, max_states: int = 1 << 22, device: int = 0):
+    ``table_graph``: the support graph of a truth-table network, ``"stg"`` or ``"step"`` (module
+    docstring). ``None`` with a truth-table network is refused (``PBN_E_UNSUPPORTED``): neither
+    graph is a default. A predictor-mix network has one graph and takes no ``table_graph``.
+    """
+
+    def __init__(self, net, max_states: int = 1 << 22, device: int = 0, table_graph: Optional[str] = None):
+        if table_graph is not None and table_graph not in TABLE_GRAPHS:
+            raise ValueError(f"table_graph={table_graph!r}: expected one of {sorted(TABLE_GRAPHS)} or None")
         self.net = net if isinstance(net, Net) else Net(net)
         self.n_nodes, self.n_words = self.net.n_nodes, self.net.n_words
+        self.table_graph = table_graph
         h = C.c_void_p()
-        L.check(L.lib.pbn_reach_create(self.net.handle, int(device), int(max_states), C.byref(h)))
+        if table_graph is None:
+            L.check(L.lib.pbn_reach_create(self.net.handle, int(device), int(max_states), C.byref(h)))
+        else:
+            if self.net.kind != KIND_PROB_TABLE:
+                raise ValueError("table_graph applies to truth-table networks; a predictor-mix network has one graph")
+            L.check(L.lib.pbn_reach_create_table(self.net.handle, int(device), int(max_states),
+                                                 TABLE_GRAPHS[table_graph], C.byref(h)))
         self._h = h
 
     def close(self):
@@ -108,6 +137,22 @@ class ReachSet:
         o = np.empty(self.n_words, dtype=np.uint64)
         L.check(L.lib.pbn_reach_hull(self._h, L.ptr(a, L._u64p), L.ptr(o, L._u64p)))
         return a, o
+
+
+def host_unstable(net, states, table_graph: Optional[str] = None) -> np.ndarray:
+    """:meth:`ReachSet.unstable` without a device (``pbn_net_unstable``): the same rule definition the
+    kernels evaluate, run over the host copy of the network image. ``table_graph`` is required for a
+    truth-table network and ignored for a predictor-mix one."""
+    net = net if isinstance(net, Net) else Net(net)
+    graph = 0
+    if net.kind == KIND_PROB_TABLE:
+        if table_graph not in TABLE_GRAPHS:
+            raise ValueError(f"table_graph={table_graph!r}: expected one of {sorted(TABLE_GRAPHS)}")
+        graph = TABLE_GRAPHS[table_graph]
+    w = np.ascontiguousarray(states, dtype=np.uint64).reshape(-1, net.n_words)
+    out = np.empty_like(w)
+    L.check(L.lib.pbn_net_unstable(net.handle, graph, L.ptr(w, L._u64p), w.shape[0], L.ptr(out, L._u64p)))
+    return out
 
 
 # ---------------------------------------------------------------- host helpers
@@ -203,6 +248,11 @@ class AttractorResult:
         cubes (``pbn_envcfg_create`` accepts 4,096)."""
         return [cube_cover(a, self.n_nodes, max_cubes) for a in self.attractors]
 
+    def states_lists(self) -> list:
+        """Per attractor the list of its states as tuples of ints, node 0 first, in the arrays' order:
+        the form ``PBNEnv`` / ``VecPBNEnv`` take as ``all_attractors``."""
+        return [[tuple(int(v) for v in row) for row in unpack_bits(a, self.n_nodes)] for a in self.attractors]
+
 
 def _known(found, s) -> int:
     """Index of the found attractor holding state ``s``, or -1. Attractors are disjoint, so one state decides."""
@@ -231,8 +281,14 @@ def _descend(work: ReachSet, s: np.ndarray, found=()):
 
 
 def find_attractors(network, n_seeds: int = 4096, burn_in: Optional[int] = None, max_states: int = 1 << 22,
-                    seed: int = 0, device: int = 0, states=None) -> AttractorResult:
-    """Attractors of a predictor-mix network reached from simulated (or given) states.
+                    seed: int = 0, device: int = 0, states=None, table_graph: str = "stg") -> AttractorResult:
+    """Attractors of a network reached from simulated (or given) states.
+
+    ``table_graph`` names the support graph of a truth-table network (``"stg"``: the graph of
+    ``PBNEnv.compute_attractors``; ``"step"``: the graph ``PBN.step`` walks, node 0 frozen); it is
+    ignored for a predictor-mix network, which has one graph. The simulation of a truth-table network
+    clears node 0 and never updates it, so sampled seeds all have ``x_0 = 0``: under ``"stg"`` an attractor
+    that only states with ``x_0 = 1`` reach is found from ``states=`` alone.
 
     Seeds are ``PBNBatch.randomize()`` + ``rollout(burn_in)`` (default ``1024 * N`` updates) of
     ``n_seeds`` envs, or ``states`` (packed ``[S][W]``; no burn-in). Duplicate seeds and seeds
@@ -246,11 +302,14 @@ def find_attractors(network, n_seeds: int = 4096, burn_in: Optional[int] = None,
 
     Membership is exact, coverage is sampled: every array under ``attractors`` is exactly an
     attractor of the support graph (defined on the 53-bit selection thresholds, see the module
-    docstring); attractors that no seed reaches are missing.
+    docstring, or on the 53-bit table thresholds); attractors that no seed reaches are missing.
     """
     net = network if isinstance(network, Net) else Net(network)
     N, W = net.n_nodes, net.n_words
-    work = ReachSet(net, max_states, device)  # refuses truth-table networks
+    graph = table_graph if net.kind == KIND_PROB_TABLE else None
+    if net.kind == KIND_PROB_TABLE and graph not in TABLE_GRAPHS:
+        raise ValueError(f"table_graph={table_graph!r}: expected one of {sorted(TABLE_GRAPHS)}")
+    work = ReachSet(net, max_states, device, table_graph=graph)
     if states is None:
         b = PBNBatch(net, int(n_seeds), device=device, seed=seed)
         b.randomize()
@@ -278,7 +337,7 @@ def find_attractors(network, n_seeds: int = 4096, burn_in: Optional[int] = None,
     basin = None
     try:
         if len(uniq) > 1:
-            basin = ReachSet(net, max_states, device)
+            basin = ReachSet(net, max_states, device, table_graph=graph)
             if not basin.closure(uniq)[1]:
                 basin.close()
                 basin = None
@@ -341,5 +400,26 @@ def resolve_all_attractors(network, all_attractors, device: int = 0, seed: int =
     return res.all_attractors()
 
 
-__all__ = ["ReachSet", "AttractorResult", "find_attractors", "cube_cover", "expand_cubes", "hull_cube", "rows_in",
-           "sort_rows", "resolve_all_attractors", "MAX_ENV_CUBES"]
+def find_state_attractors(network, device: int = 0, seed: int = 0) -> list:
+    """``all_attractors="find"`` of ``PBNEnv`` / ``VecPBNEnv``: the attractors of a truth-table network's
+    ``"stg"`` graph (what :func:`gym_pbn_amd.stg.compute_attractors` enumerates ``2**N`` states for), found by
+    :func:`find_attractors` and expanded to lists of state tuples. Raises ``RuntimeError`` if nothing was
+    enumerated, ``ValueError`` past ``MAX_ENV_STATES`` states in all; warns when some closures were incomplete."""
+    res = find_attractors(network, device=device, seed=seed, table_graph="stg")
+    if not res.attractors:
+        raise RuntimeError(f"no attractor fits the state set: {len(res.incomplete)} closure(s) ran past max_states")
+    if res.incomplete:
+        import warnings
+
+        warnings.warn(f"{sum(e['n_seeds'] for e in res.incomplete)} seed(s) ended in closures past max_states; "
+                      "the env uses the attractors that were enumerated")
+    total = sum(len(a) for a in res.attractors)
+    if total > MAX_ENV_STATES:
+        raise ValueError(f"the attractors hold {total} states; the env keeps them as Python sets and takes at most "
+                         f"{MAX_ENV_STATES}")
+    return res.states_lists()
+
+
+__all__ = ["ReachSet", "AttractorResult", "host_unstable", "find_attractors", "cube_cover", "expand_cubes", "hull_cube", "rows_in",
+           "sort_rows", "resolve_all_attractors", "find_state_attractors", "MAX_ENV_CUBES", "MAX_ENV_STATES",
+           "TABLE_GRAPHS"]

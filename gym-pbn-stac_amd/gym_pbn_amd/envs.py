@@ -23,7 +23,7 @@ import numpy as np
 
 from . import spaces
 from . import _lib as L
-from .attractors import resolve_all_attractors
+from .attractors import find_state_attractors, resolve_all_attractors
 from .batch import EnvConfig, Net, PBNBatch, pack_bits, unpack_bits
 from .network import PredictorNetwork, TruthTableNetwork, load_network
 
@@ -103,17 +103,21 @@ class PBN:
     def __init__(self, PBN_data=None, logic_func_data=None, network: Optional[TruthTableNetwork] = None,
                  device: int = 0, seed: int = 0, env_id: int = 0):
         if network is None:
-            if PBN_data is not None and len(PBN_data) != 0:
-                network = TruthTableNetwork.from_pbn_data(PBN_data)
-            elif logic_func_data is not None:
-                network = TruthTableNetwork.from_logic_funcs(*logic_func_data)
-            else:
-                raise ValueError("PBN needs PBN_data or logic_func_data")
+            network = self.table_network(PBN_data, logic_func_data)
         self.network = network
         self.N = network.n_nodes
         self._device, self._env_id = device, env_id
         self._b = PBNBatch(Net(network), 1, device=device, env_id_base=env_id, seed=seed)
         self._replay: deque = deque()
+
+    @staticmethod
+    def table_network(PBN_data=None, logic_func_data=None) -> TruthTableNetwork:
+        """The network of the constructor's arguments (``pbn.py:15-51``), without a device."""
+        if PBN_data is not None and len(PBN_data) != 0:
+            return TruthTableNetwork.from_pbn_data(PBN_data)
+        if logic_func_data is not None:
+            return TruthTableNetwork.from_logic_funcs(*logic_func_data)
+        raise ValueError("PBN needs PBN_data or logic_func_data")
 
     @property
     def state(self) -> np.ndarray:
@@ -164,6 +168,8 @@ class VecPBNEnv:
     reward +20 and terminated when the state is in ``target_nodes`` (expanded by the
     attractors that meet it, :57-59), else -4 and another -1 for an action; truncated
     is always False. Rewards are computed on the host from the packed states.
+    ``all_attractors``: as for :class:`PBNEnv` (``None``: the full STG; ``"find"``: device
+    discovery; a list: taken as given).
     ``auto_reset`` resets ended envs to a state drawn uniformly from the attracting set
     (SB3 VecEnv convention; the reference env never resets itself).
     """
@@ -181,6 +187,8 @@ class VecPBNEnv:
             from .stg import compute_attractors
 
             all_attractors = compute_attractors(net)
+        elif isinstance(all_attractors, str) and all_attractors == "find":  # opt-in: found on the device
+            all_attractors = find_state_attractors(net, device=device, seed=seed)
         self.all_attractors = [set(tuple(int(v) for v in s) for s in a) for a in all_attractors]
         target = set(goal_config["target_nodes"])
         for attractor in self.all_attractors:
@@ -425,7 +433,11 @@ class PBNEnv:
 
     Same constructor as the reference. ``all_attractors`` are derived from the full
     asynchronous STG (:func:`gym_pbn_amd.stg.compute_attractors`, ``pbn_env.py:54``)
-    unless given with the keyword-only ``all_attractors`` (needed past ~20 nodes).
+    unless given with the keyword-only ``all_attractors`` (needed past ~20 nodes):
+    a list of attractors (each an iterable of state tuples) is taken as given, and
+    ``"find"`` has them found on the device by reachability from simulated states
+    (:func:`gym_pbn_amd.attractors.find_attractors` on the same ``"stg"`` graph; exact
+    attractors, sampled coverage; at most 2**16 states in all).
     ``goal_config["target_nodes"]`` (a set of state tuples) is required as in the
     reference (``:44-51``). Host-side draws (``reset``'s ``random.choice`` calls) come
     from a per-env ``random.Random`` that ``reset(seed)`` seeds like ``random.seed``
@@ -435,7 +447,11 @@ class PBNEnv:
     def __init__(self, render_mode: str = "human", render_no_cache: bool = False, PBN_data=None,
                  logic_func_data=None, name: str = None, goal_config: dict = None, reward_config: dict = None,
                  *, all_attractors=None, device: int = 0, seed: int = 0):
-        self.PBN = PBN(PBN_data, logic_func_data, device=device, seed=seed)
+        network = None
+        if isinstance(all_attractors, str) and all_attractors == "find":  # opt-in: found on the device
+            network = PBN.table_network(PBN_data, logic_func_data)
+            all_attractors = find_state_attractors(network, device=device, seed=seed)
+        self.PBN = PBN(PBN_data, logic_func_data, network=network, device=device, seed=seed)
         goal_config = self._check_config(goal_config, "goal", {"target", "all_attractors"})
         if goal_config is None or "target_nodes" not in goal_config:
             raise KeyError("target_nodes")  # pbn_env.py:51

@@ -7,7 +7,9 @@ where the reference ships their predictor sets; attractors (the reference runs t
 external ``cabean`` binary, ``get_attractors_from_cabean.py:39-54``) must be passed as
 ``all_attractors`` (``gym_pbn_amd.io.cabean.attractors_list`` parses cabean's output), or
 ``all_attractors="find"`` has :func:`gym_pbn_amd.attractors.find_attractors` discover them on the
-device (opt-in; ``None`` still raises).
+device (opt-in; ``None`` still raises). ``gym-PBN/PBN-v0`` (``PBNEnv``) forwards the same keyword: ``None``
+there is the full STG (:mod:`gym_pbn_amd.stg`, up to 22 nodes) and ``"find"`` the device discovery on the
+truth-table network's ``"stg"`` graph.
 ``max_episode_steps=100`` (a gymnasium TimeLimit in the reference) is the envs'
 ``horizon``.
 """

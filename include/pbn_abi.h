@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define PBN_ABI_VERSION 16
+#define PBN_ABI_VERSION 17
 
 enum {
     PBN_OK = 0,
@@ -140,6 +140,13 @@ void pbn_net_destroy(pbn_net *net);
  * tests: equals the record of predictor min(#{q : u32_k53(a) >= thr_q}, count - 1)
  * (Predstep's choice, base.py:94-97). */
 int pbn_net_select_u32(const pbn_net *net, int32_t node, uint32_t a, uint64_t *record);
+/* The support graphs' edge rule (see "attractor discovery" below) on the host copy of the network image, no
+ * device: states [S][W] -> masks [S][W], bit i set iff node i can flip at that state. It is the one definition
+ * the kernels of pbn_reach_* evaluate (csrc/pbn_reach_rule.hpp), so it pins the rule on a machine without a GPU.
+ * PROB_TABLE networks: graph = PBN_TABLE_GRAPH_STG or PBN_TABLE_GRAPH_STEP, anything else PBN_E_INVALID.
+ * PREDICTOR_MIX networks have one graph: `graph` is ignored. */
+enum { PBN_TABLE_GRAPH_STG = 1, PBN_TABLE_GRAPH_STEP = 2 };
+int pbn_net_unstable(const pbn_net *net, int32_t graph, const uint64_t *states, uint64_t n_states, uint64_t *masks);
 
 /* ---- batches of independent envs (the reference holds one Graph per env) ---- */
 /* Tuning knobs, read from the environment once here (measurement and tests only):
@@ -296,10 +303,18 @@ int pbn_env_grid_stats(pbn_batch *b, uint32_t *stats);
 /* ---- attractor discovery: Graph.getNextStates / genSTG (base.py:221-242) + findAttractors (base.py:398-399) ----
  * The reference enumerates all 2^N states on the host ("too big for PBN > 10") and otherwise shells out to the
  * cabean binary. Here a pbn_reach is an exact set of packed states on the device, grown by reachability in the
- * SUPPORT GRAPH of a predictor-mix network: x -> x ^ (1 << i) iff some live predictor of node i outputs 1 - x_i at
+ * SUPPORT GRAPH of a network.
+ * PREDICTOR_MIX: x -> x ^ (1 << i) iff some live predictor of node i outputs 1 - x_i at
  * x (getNextStates keeps an edge when prob > 0). A predictor is live iff its selection interval on the 53-bit
  * grid is non-empty (pred_thr, the last threshold taken as 2^53) -- the rule is defined on the 53-bit thresholds,
- * not on the Philox stream's 32-bit choice grid. An attractor is a terminal strongly connected component
+ * not on the Philox stream's 32-bit choice grid.
+ * PROB_TABLE: with T = thr[entry of node i's table at x] = ceil(p * 2^53), x -> x ^ (1 << i) iff (x_i = 0 and
+ * T > 0) or (x_i = 1 and T < 2^53) -- exactly the reference's prob_true > 0. / prob_true < 1. (pbn.py:186-199): a
+ * double p > 0 has ceil(p * 2^53) >= 1, a double p < 1 has p * 2^53 <= 2^53 - 1 with no rounding. The family has
+ * two graphs and the caller names one: PBN_TABLE_GRAPH_STG, nodes 0 .. N-1 may move (PBN._compute_next_states, the
+ * graph behind PBNEnv.compute_attractors); PBN_TABLE_GRAPH_STEP, nodes 1 .. N-1 only (the graph PBN.step walks,
+ * pbn.py:90 randint(1, N-1); reset clears node 0).
+ * An attractor is a terminal strongly connected component
  * (nx.attracting_components on the reference's STG); gym_pbn_amd/attractors.py finds them with these calls.
  * One pbn_reach = one device + one HIP stream; calls on it are synchronous and must be serialised by the caller. */
 #define PBN_REACH_MAX_STATES ((uint64_t)1 << 28)
@@ -312,9 +327,17 @@ typedef struct {
                               BFS level takes it again) */
     uint64_t n_states;     /* live states */
     uint64_t n_entries;    /* key entries in use */
+    int32_t kind;          /* the network's PBN_KIND_* */
+    int32_t table_graph;   /* PBN_TABLE_GRAPH_* of a PROB_TABLE set, 0 for PREDICTOR_MIX */
 } pbn_reach_info;
-/* PROB_TABLE networks: PBN_E_UNSUPPORTED (gym_pbn_amd/stg.py is their route). device < 0: PBN_E_RANGE. */
+/* PREDICTOR_MIX networks. PROB_TABLE networks: PBN_E_UNSUPPORTED (their set takes a graph: pbn_reach_create_table).
+ * device < 0: PBN_E_RANGE. */
 int pbn_reach_create(const pbn_net *net, int device, uint64_t max_states, pbn_reach **out);
+/* PROB_TABLE networks: the set over the support graph `graph` (PBN_TABLE_GRAPH_STG / _STEP); every other
+ * pbn_reach_* call works on the result as on a predictor-mix set. A PREDICTOR_MIX network or an unknown graph:
+ * PBN_E_INVALID. The kernels stage the whole network image in LDS (TT-200: 28.8 KiB); an image that does not fit
+ * what they request is refused here with PBN_E_UNSUPPORTED. */
+int pbn_reach_create_table(const pbn_net *net, int device, uint64_t max_states, int32_t graph, pbn_reach **out);
 void pbn_reach_destroy(pbn_reach *r);
 int pbn_reach_get_info(const pbn_reach *r, pbn_reach_info *info);
 /* The edge rule alone (base.py:221-242, one state's row of getNextStates): host states [S][W] -> masks [S][W], bit i

@@ -1,0 +1,233 @@
+"""Attractor discovery for truth-table networks on the device: the edge-rule kernels for both support graphs,
+the state set over them, ``find_attractors`` and the env switch.
+
+The independent statement of the rule is ``np_tt_unstable`` in ``test_attractors_tt_host.py``; golden ``"stg"``
+attractors come from the reference's ``PBN.print_STG`` + ``attracting_components``
+(``tests/golden/attractors_tt_small.json``), ``"step"`` ones from the restatement with node 0 frozen.
+"""
+
+import numpy as np
+import pytest
+
+from test_attractors_host import all_states, lift_states
+from test_attractors_tt_host import (CASES, GRAPHS, case_by, case_id, case_network, case_pbn_data, copies_network,
+                                     copies_pbn_data, edge_value_network, embed_tt_network, expected_attractors,
+                                     np_tt_unstable_words, product_states)
+
+pytestmark = pytest.mark.gpu
+
+SMALL = 1 << 13  # max_states for the fixture nets (n <= 12)
+
+
+# ---------------------------------------------------------------- unstable against the numpy rule
+@pytest.mark.parametrize("graph", GRAPHS)
+@pytest.mark.parametrize("c", CASES, ids=case_id)
+def test_unstable_fixture_nets(c, graph):
+    from gym_pbn_amd.attractors import ReachSet
+
+    net = case_network(c)
+    states = all_states(c["n_nodes"])
+    rs = ReachSet(net, 64, table_graph=graph)
+    assert np.array_equal(rs.unstable(states), np_tt_unstable_words(net, states, graph))
+    info = rs.info()
+    assert (info["kind"], info["table_graph"]) == (2, {"stg": 1, "step": 2}[graph])
+
+
+@pytest.mark.parametrize("graph", GRAPHS)
+def test_unstable_tt200(graph):
+    """W = 4, four inputs per node, the 28.8 KiB image; 257 states: an odd tail and more than one workgroup."""
+    from gym_pbn_amd.attractors import ReachSet
+    from gym_pbn_amd.batch import pack_bits
+    from gym_pbn_amd.network import load_network
+
+    net = load_network("tt200")
+    states = pack_bits(np.random.default_rng(3).integers(0, 2, size=(257, net.n_nodes), dtype=np.uint8))
+    got = ReachSet(net, 64, table_graph=graph).unstable(states)
+    assert got.shape == (257, 4)
+    assert np.array_equal(got, np_tt_unstable_words(net, states, graph))
+
+
+@pytest.mark.parametrize("graph", GRAPHS)
+@pytest.mark.parametrize("n_total", [64, 65])
+def test_unstable_embedded_across_the_word_boundary(n_total, graph):
+    """The edge-value network (k = 0 .. 6 side by side in one wave, tables holding the doubles next to 0 and 1)
+    inside 64 / 65 nodes, its nodes ending at bit 63 / straddling bits 63 and 64."""
+    from gym_pbn_amd.attractors import ReachSet
+
+    small = edge_value_network()
+    n = small.n_nodes
+    place = list(range(n_total - n, n_total))
+    big = embed_tt_network(small, n_total, place)
+    frozen = np.random.default_rng(5).integers(0, 2, size=n_total, dtype=np.uint8)
+    states = lift_states(all_states(n), n, n_total, place, frozen)
+    got = ReachSet(big, 64, table_graph=graph).unstable(states)
+    assert np.array_equal(got, np_tt_unstable_words(big, states, graph))
+    want = lift_states(np_tt_unstable_words(small, all_states(n), "stg"), n, n_total, place, np.zeros(n_total, np.uint8))
+    assert np.array_equal(got, want)  # frozen nodes never flip; the small net's node 0 is not the big one's
+
+
+# ---------------------------------------------------------------- fixture nets end to end
+@pytest.mark.parametrize("graph", GRAPHS)
+@pytest.mark.parametrize("c", CASES, ids=case_id)
+def test_fixture_attractors_from_all_states(c, graph):
+    from gym_pbn_amd.attractors import find_attractors
+
+    net = case_network(c)
+    res = find_attractors(net, states=all_states(c["n_nodes"]), max_states=SMALL, table_graph=graph)
+    want = expected_attractors(c, graph)
+    assert not res.incomplete
+    assert [len(a) for a in res.attractors] == [len(a) for a in want]
+    for got, w in zip(res.attractors, want):
+        assert np.array_equal(got, w)
+    assert sum(res.seed_counts) == 1 << c["n_nodes"]
+    assert all(n >= len(a) for n, a in zip(res.seed_counts, res.attractors))
+
+
+# ---------------------------------------------------------------- past the enumeration limit
+BASE = (12, 3, 0.47, 8)  # three fixed points under "stg", four under "step"
+
+
+def product_fixed_points(graph):
+    """The attractors of six side-by-side copies: every product of the copies' fixed points. ``"step"`` freezes
+    global node 0 only, so copy 0 alone takes its step graph."""
+    c = case_by(*BASE)
+    others = np.concatenate(expected_attractors(c, "stg"))
+    first = np.concatenate(expected_attractors(c, graph))
+    assert all(len(a) == 1 for a in expected_attractors(c, graph))
+    return product_states([first] + [others] * 5, 12)
+
+
+def transient_seeds(graph, count):
+    """States transient in one copy and fixed in the others: each one's closure holds at most 4,096 states."""
+    c = case_by(*BASE)
+    others = np.concatenate(expected_attractors(c, "stg"))
+    first = np.concatenate(expected_attractors(c, graph))
+    rows = []
+    for q in range(count):
+        m = q % 6
+        fixed_m = first if m == 0 else others
+        free = np.setdiff1d(np.arange(1 << 12, dtype=np.uint64), fixed_m[:, 0])
+        parts = [(first if j == 0 else others)[[q % len(first if j == 0 else others)]] for j in range(6)]
+        parts[m] = free[[(q * 61) % len(free)]].reshape(1, 1)
+        rows.append(product_states(parts, 12))
+    return np.concatenate(rows)
+
+
+@pytest.mark.parametrize("graph", GRAPHS)
+def test_72_nodes_product_of_fixed_points(graph):
+    from gym_pbn_amd.attractors import _row_keys, find_attractors
+    from gym_pbn_amd.stg import MAX_STG_NODES
+
+    big = copies_network(case_by(*BASE), 6)
+    assert big.n_nodes == 72 > MAX_STG_NODES and big.n_words == 2
+    fixed = product_fixed_points(graph)
+    assert len(fixed) == {"stg": 3 ** 6, "step": 4 * 3 ** 5}[graph]
+    seeds = np.concatenate([fixed, transient_seeds(graph, 64)])
+    assert len(np.unique(seeds, axis=0)) == len(seeds)
+    res = find_attractors(big, states=seeds, max_states=1 << 16, table_graph=graph)
+    assert not res.incomplete
+    assert all(a.shape == (1, 2) for a in res.attractors)
+    got = np.concatenate(res.attractors)
+    assert len(got) == len(fixed)
+    assert np.array_equal(np.sort(_row_keys(got)), np.sort(_row_keys(fixed)))
+    assert sum(res.seed_counts) == len(seeds)
+
+
+def test_72_nodes_sampled_seeds():
+    """Coverage is sampled: what is reported is exact, how much is found is not asserted."""
+    from gym_pbn_amd.attractors import find_attractors, rows_in
+
+    big = copies_network(case_by(*BASE), 6)
+    fixed = product_fixed_points("step")
+    res = find_attractors(big, n_seeds=256, max_states=1 << 16, seed=5, table_graph="step")
+    print("72 nodes, step graph:", len(res.attractors), "attractors from 256 seeds, incomplete",
+          [(e["n_seen"], e["n_seeds"]) for e in res.incomplete])
+    for a in res.attractors:
+        assert a.shape == (1, 2) and rows_in(a, fixed).all()
+    assert sum(res.seed_counts) + sum(e["n_seeds"] for e in res.incomplete) == 256
+
+
+# ---------------------------------------------------------------- capacity
+def test_capacity_is_a_normal_return():
+    from gym_pbn_amd.attractors import ReachSet, find_attractors, rows_in
+
+    c = case_by(12, 3, 0.47, 1)
+    net = case_network(c)
+    att = expected_attractors(c, "stg")[0]
+    K = len(att)
+    assert K == 3108
+    seed = att[:1]
+    rs = ReachSet(net, K, table_graph="stg")
+    assert rs.closure(seed) == (K, True)
+    assert rs.mark_backward(seed) == K
+
+    rs = ReachSet(net, K - 1, table_graph="stg")
+    n, complete = rs.closure(seed)
+    assert not complete and n >= 1
+    assert rs.info()["complete"] == 0
+    states, _ = rs.read()
+    assert len(states) == n and len(np.unique(states, axis=0)) == n
+    assert rows_in(states, att).all()  # what it holds is inside the attractor
+
+    res = find_attractors(net, states=seed, max_states=K - 1, table_graph="stg")
+    assert not res.attractors and len(res.incomplete) == 1
+    assert res.incomplete[0]["n_seeds"] == 1 and res.incomplete[0]["n_seen"] >= 1
+
+
+# ---------------------------------------------------------------- refusals
+def test_refusals():
+    from gym_pbn_amd import _lib as L
+    from gym_pbn_amd.attractors import ReachSet, find_attractors
+    from gym_pbn_amd.network import load_network
+
+    tt8 = load_network("tt8")
+    with pytest.raises(L.PbnError) as e:
+        ReachSet(tt8, 64)  # neither graph is a default
+    assert e.value.code == L.PBN_E_UNSUPPORTED
+    with pytest.raises(ValueError):
+        ReachSet("bittner28", 64, table_graph="stg")
+    with pytest.raises(ValueError):
+        ReachSet(tt8, 64, table_graph="sync")
+    with pytest.raises(ValueError):
+        find_attractors(tt8, states=all_states(8), table_graph=None)
+    rs = ReachSet(tt8, 64, table_graph="step")  # and the named graphs are served
+    assert rs.unstable(all_states(8)).shape == (256, 1)
+
+
+# ---------------------------------------------------------------- the env switch
+def test_envs_from_found_attractors_72_nodes():
+    from gym_pbn_amd.batch import unpack_bits
+    from gym_pbn_amd.envs import PBNEnv, VecPBNEnv
+
+    data = copies_pbn_data(case_by(*BASE), 6)
+    goal = {"target_nodes": {(0,) * 72}, "all_attractors": None, "target": None}
+    fixed = {tuple(int(v) for v in row) for row in unpack_bits(product_fixed_points("stg"), 72)}
+
+    env = PBNEnv(PBN_data=data, goal_config=goal, all_attractors="find", seed=1)
+    assert env.all_attractors and all(a <= fixed and len(a) == 1 for a in env.all_attractors)
+    obs, _ = env.reset(seed=2)
+    assert tuple(int(x) for x in obs) in env.attracting_states
+    for t in range(20):
+        obs, reward, terminated, truncated, _ = env.step(t % 3)
+        assert obs.shape == (72,) and reward in (20, -4, -5) and not truncated
+
+    vec = VecPBNEnv(PBN_data=data, goal_config=goal, n_envs=64, all_attractors="find", seed=1)
+    assert vec.all_attractors and all(a <= fixed for a in vec.all_attractors)
+    attracting = set.union(*vec.all_attractors)
+    bits = vec.reset()
+    assert bits.shape == (64, 72) and all(tuple(int(v) for v in row) in attracting for row in bits)
+    for t in range(20):
+        obs, reward, term, trunc, _ = vec.step(np.full(64, t % 3))
+        assert obs.shape == (64, 72) and not trunc.any()
+
+
+def test_find_equals_the_full_stg_on_a_12_node_net():
+    """One 3,108-state attractor: every seed descends to it, so sampled coverage is full coverage here."""
+    from gym_pbn_amd.envs import PBNEnv
+
+    c = case_by(12, 3, 0.47, 1)
+    goal = {"target_nodes": {(0,) * 12}, "all_attractors": None, "target": None}
+    found = PBNEnv(PBN_data=case_pbn_data(c), goal_config=goal, all_attractors="find")
+    full = PBNEnv(PBN_data=case_pbn_data(c), goal_config=goal, all_attractors=None)
+    assert {frozenset(a) for a in found.all_attractors} == {frozenset(a) for a in full.all_attractors}
+    assert {frozenset(a) for a in found.all_attractors} == {frozenset(tuple(s) for s in a) for a in c["attractors"]}

@@ -11,6 +11,10 @@ expanded), so a 2^21-state closure does not take minutes of host time.
 
 Networks under ``--large`` (Bittner-149, -199: closures that do not fit) only get the ``find_attractors``
 report: how many states each closure had seen when it stopped and how many nodes vary among them.
+Truth-table networks (``--tables``, support graph ``--table-graph``): a bundled name such as ``tt200``, or
+``n,k,det,seed`` for a random network (every node ``k`` inputs, table entries 0.0 / 1.0 with probability
+``det`` each, else uniform). They get the ``find_attractors`` report and the closure rate from one seed; a
+closure that stops at ``--table-max-states`` still gives a rate (states seen per second).
 Prints one JSON line per network.
 """
 
@@ -30,8 +34,37 @@ sys.path.insert(0, str(ROOT / "gym-pbn-stac_amd"))
 TWO53 = 1 << 53
 
 
-def np_unstable(net, bits):
+def random_table_network(n, k, det, seed):
+    from gym_pbn_amd.network import TruthTableNetwork
+
+    rng = np.random.default_rng(seed)
+    data = []
+    for i in range(n):
+        inp = np.sort(rng.choice([j for j in range(n) if j != i], size=k, replace=False))
+        u, v = rng.random(1 << k), rng.random(1 << k)
+        mask = np.zeros(n, dtype=bool)
+        mask[inp] = True
+        data.append((mask, np.where(u < det, 0.0, np.where(u < 2 * det, 1.0, v)).reshape((2,) * k), f"n{i}", False))
+    return TruthTableNetwork.from_pbn_data(data, name=f"random-{n}-{k}-{det}-{seed}")
+
+
+def np_table_unstable(net, bits, graph):
+    """Node i can flip iff its table entry p has p > 0 (from 0) or p < 1 (from 1); "step" freezes node 0."""
+    bits = np.asarray(bits, dtype=np.int64)
+    out = np.zeros(bits.shape, dtype=bool)
+    for i in range(1 if graph == "step" else 0, net.n_nodes):
+        code = np.zeros(len(bits), dtype=np.int64)
+        for j in net.inputs[int(net.input_offsets[i]):int(net.input_offsets[i + 1])]:
+            code = 2 * code + bits[:, int(j)]
+        p = net.probs[int(net.thr_offsets[i]):int(net.thr_offsets[i + 1])][code]
+        out[:, i] = ((p > 0.0) & (bits[:, i] == 0)) | ((p < 1.0) & (bits[:, i] == 1))
+    return out
+
+
+def np_unstable(net, bits, graph=None):
     """Node i can flip at a state iff a live predictor (non-empty 53-bit interval) outputs 1 - x_i."""
+    if graph is not None:
+        return np_table_unstable(net, bits, graph)
     bits = np.asarray(bits, dtype=np.int64)
     out = np.zeros(bits.shape, dtype=bool)
     for i in range(net.n_nodes):
@@ -48,7 +81,7 @@ def np_unstable(net, bits):
     return out
 
 
-def np_closure(net, seed, limit):
+def np_closure(net, seed, limit, graph=None):
     """Breadth-first closure; returns (states seen, states expanded)."""
     from gym_pbn_amd.attractors import rows_in
     from gym_pbn_amd.batch import unpack_bits
@@ -56,7 +89,7 @@ def np_closure(net, seed, limit):
     seen = np.asarray(seed, np.uint64).reshape(1, -1)
     frontier, expanded = seen, 0
     while len(frontier) and len(seen) < limit:
-        s_idx, i_idx = np.nonzero(np_unstable(net, unpack_bits(frontier, net.n_nodes)))
+        s_idx, i_idx = np.nonzero(np_unstable(net, unpack_bits(frontier, net.n_nodes), graph))
         succ = frontier[s_idx].copy()
         succ[np.arange(len(s_idx)), i_idx // 64] ^= np.uint64(1) << (i_idx % 64).astype(np.uint64)
         expanded += len(frontier)
@@ -75,6 +108,10 @@ def main():
     ap.add_argument("--n-seeds", type=int, default=256)
     ap.add_argument("--max-states", type=int, default=1 << 22)
     ap.add_argument("--numpy-limit", type=int, default=1 << 18)
+    ap.add_argument("--tables", nargs="*", default=["tt200", "40,3,0.40,7"])
+    ap.add_argument("--table-graph", choices=["stg", "step"], default="stg")
+    ap.add_argument("--table-seeds", type=int, default=64)
+    ap.add_argument("--table-max-states", type=int, default=1 << 20)
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args()
 
@@ -82,12 +119,16 @@ def main():
     from gym_pbn_amd.network import load_network
 
     ReachSet("bittner28", 64, a.device).closure(np.zeros((1, 1), np.uint64))  # runtime and code object warm
-    for name in a.networks:
-        net = load_network(name)
+    jobs = [(name, load_network(name), None, a.n_seeds, a.max_states) for name in a.networks]
+    for name in a.tables:
+        net = random_table_network(*(float(v) if "." in v else int(v) for v in name.split(","))) if "," in name \
+            else load_network(name)
+        jobs.append((net.name, net, a.table_graph, a.table_seeds, a.table_max_states))
+    for name, net, graph, n_seeds, max_states in jobs:
         t0 = time.perf_counter()
-        res = find_attractors(net, n_seeds=a.n_seeds, max_states=a.max_states, device=a.device)
+        res = find_attractors(net, n_seeds=n_seeds, max_states=max_states, device=a.device, table_graph=graph or "stg")
         t_find = time.perf_counter() - t0
-        out = {"network": name, "n_seeds": a.n_seeds, "max_states": a.max_states,
+        out = {"network": name, "table_graph": graph, "n_seeds": n_seeds, "max_states": max_states,
                "attractor_sizes": [len(x) for x in res.attractors], "seed_counts": res.seed_counts,
                "attractors_disjoint": not any(rows_in(x[:1], y)[0] for k, x in enumerate(res.attractors)
                                               for y in res.attractors[k + 1:]),
@@ -95,7 +136,7 @@ def main():
                               for e in res.incomplete],
                "find_attractors_s": round(t_find, 4)}
         seed = res.attractors[-1][:1] if res.attractors else res.incomplete[0]["seed"][None]
-        rs = ReachSet(net, a.max_states, a.device)
+        rs = ReachSet(net, max_states, a.device, table_graph=graph)
         t0 = time.perf_counter()
         n, complete = rs.closure(seed)
         t_dev = time.perf_counter() - t0
@@ -107,7 +148,7 @@ def main():
                    device_states_per_s=round(n / t_dev), backward_marked=n_back, backward_s=round(t_back, 5),
                    dead_entries=int(info["n_entries"] - info["n_states"]))
         t0 = time.perf_counter()
-        seen, expanded = np_closure(net, seed, a.numpy_limit)
+        seen, expanded = np_closure(net, seed, a.numpy_limit, graph)
         t_np = time.perf_counter() - t0
         out.update(numpy_states_seen=seen, numpy_states_expanded=expanded, numpy_s=round(t_np, 3),
                    numpy_states_per_s=round(expanded / t_np), numpy_stopped_early=bool(seen < n))
