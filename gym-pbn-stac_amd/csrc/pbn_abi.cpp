@@ -226,7 +226,9 @@ int pbn_batch_create(const pbn_net* net_c, int device, uint64_t n_envs, uint64_t
     *out = nullptr;
     pbn_net* net = const_cast<pbn_net*>(net_c);
     if (n_envs < 1) return fail(PBN_E_INVALID, "n_envs must be >= 1");
-    if (env_id_base + n_envs > ((uint64_t)1 << 56)) return fail(PBN_E_RANGE, "global env ids must stay below 2^56");
+    // without the sum: env_id_base + n_envs wraps for bases near 2^64
+    const uint64_t id_end = (uint64_t)1 << 56;
+    if (n_envs > id_end || env_id_base > id_end - n_envs) return fail(PBN_E_RANGE, "global env ids must stay below 2^56");
     if (int rc = open_device(device)) return rc;
     pbn_batch* b = new pbn_batch;
     b->net = net;
@@ -327,6 +329,30 @@ int pbn_batch_get_info(const pbn_batch* b, pbn_batch_info* info) {
     info->env_handoff = p.handoff ? 1 : 0;
     info->env_chunk = (p.mode == ENV_MODE_COOP || p.mode == ENV_MODE_TAIL) ? (int)p.chunk : 0;
     info->step_chains = b->step.chains;
+    return 0;
+}
+
+int pbn_batch_get_counters(const pbn_batch* b, pbn_batch_counters* out) {
+    CHECK_NN(b, "batch");
+    CHECK_NN(out, "out");
+    out->update_count = b->update_count;
+    out->ssd_iters = b->aux.ssd_iters;
+    out->sync_steps = b->aux.sync_steps;
+    out->env_call_count = b->r6.calls;
+    out->reset_count = b->reset_count;
+    return 0;
+}
+
+// Host fields only: every launch takes its counter as an argument, and the step graphs read theirs from sg.ubase,
+// which pbn_step rewrites from update_count ahead of every call that replays one (upload_update_count).
+int pbn_batch_set_counters(pbn_batch* b, const pbn_batch_counters* in) {
+    CHECK_NN(b, "batch");
+    CHECK_NN(in, "in");
+    b->update_count = in->update_count;
+    b->aux.ssd_iters = in->ssd_iters;
+    b->aux.sync_steps = in->sync_steps;
+    b->r6.calls = in->env_call_count;
+    b->reset_count = in->reset_count;
     return 0;
 }
 

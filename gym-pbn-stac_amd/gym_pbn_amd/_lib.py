@@ -72,6 +72,13 @@ class BatchInfo(C.Structure):
     ]
 
 
+class BatchCounters(C.Structure):
+    _fields_ = [
+        ("update_count", C.c_uint64), ("ssd_iters", C.c_uint64), ("sync_steps", C.c_uint64),
+        ("env_call_count", C.c_uint32), ("reset_count", C.c_uint32),
+    ]
+
+
 class EnvCfgDesc(C.Structure):
     _fields_ = [
         ("n_cubes", C.c_int32), ("cube_care", _u64p), ("cube_value", _u64p),
@@ -105,6 +112,8 @@ SIGNATURES = {
     "pbn_batch_create": (C.c_int, [_vp, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, _PP]),
     "pbn_batch_destroy": (None, [_vp]),
     "pbn_batch_get_info": (C.c_int, [_vp, C.POINTER(BatchInfo)]),
+    "pbn_batch_get_counters": (C.c_int, [_vp, C.POINTER(BatchCounters)]),
+    "pbn_batch_set_counters": (C.c_int, [_vp, C.POINTER(BatchCounters)]),
     "pbn_sync": (C.c_int, [_vp]),
     "pbn_set_state": (C.c_int, [_vp, _u64p]),
     "pbn_get_state": (C.c_int, [_vp, _u64p]),

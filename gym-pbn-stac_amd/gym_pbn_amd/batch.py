@@ -232,6 +232,29 @@ class PBNBatch:
         L.check(L.lib.pbn_batch_get_info(self._h, C.byref(i)))
         return {k: getattr(i, k) for k, _ in L.BatchInfo._fields_}
 
+    def counters(self) -> dict:
+        """The batch's position in its Philox streams (pbn_batch_counters): with the state words and
+        ``n_steps``, all a bit-exact checkpoint needs."""
+        c = L.BatchCounters()
+        L.check(L.lib.pbn_batch_get_counters(self._h, C.byref(c)))
+        return {k: getattr(c, k) for k, _ in L.BatchCounters._fields_}
+
+    def seek(self, **fields):
+        """Set the named counters (``update_count``, ``ssd_iters``, ``sync_steps``: 64 bits;
+        ``env_call_count``, ``reset_count``: 32 bits, taken modulo 2^32); the others keep their values."""
+        c = L.BatchCounters()
+        L.check(L.lib.pbn_batch_get_counters(self._h, C.byref(c)))
+        names = dict(L.BatchCounters._fields_)
+        for k, v in fields.items():
+            if k not in names:
+                raise TypeError(f"unknown counter {k!r}")
+            bits = 8 * C.sizeof(names[k])
+            v = int(v)
+            if v < 0 or (bits == 64 and v >> 64):
+                raise ValueError(f"{k}={v} outside [0, 2^{bits})")
+            setattr(c, k, v & ((1 << bits) - 1))
+        L.check(L.lib.pbn_batch_set_counters(self._h, C.byref(c)))
+
     def sync(self):
         L.check(L.lib.pbn_sync(self._h))
 

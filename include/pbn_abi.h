@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define PBN_ABI_VERSION 17
+#define PBN_ABI_VERSION 18
 
 enum {
     PBN_OK = 0,
@@ -161,6 +161,23 @@ int pbn_batch_create(const pbn_net *net, int device, uint64_t n_envs, uint64_t e
                      pbn_batch **out);
 void pbn_batch_destroy(pbn_batch *b);
 int pbn_batch_get_info(const pbn_batch *b, pbn_batch_info *info);
+/* A batch's position in its Philox streams: every draw is keyed by (seed, global env id, one of these counters), so
+ * the state words (pbn_get_state), n_steps (pbn_get_n_steps) and this struct are all a bit-exact checkpoint needs;
+ * a batch created with the same network, seed and env_id_base and given the three back continues as the first would
+ * have. update_count: pbn_step / pbn_rollout / pbn_step_forced updates so far; ssd_iters: pbn_ssd_run iterations;
+ * sync_steps: pbn_synch_step steps (the choice stream has room for sync_steps < 2^48; the two flip streams,
+ * pbn_ssd_run's and pbn_synch_step's perturbations, take the low 32 bits of their counter); env_call_count: env steps
+ * launched (pbn_env_step_multi*, += n_steps for a fused rollout); reset_count: pbn_randomize_state / pbn_env_reset*
+ * calls. The two 32-bit counters wrap modulo 2^32, also inside a fused rollout (env step t of a launch draws with
+ * (uint32_t)(env_call_count + t)). pbn_batch_set_counters takes effect from the next call on: no captured step
+ * graph holds a counter (replays read it from device memory, written by every pbn_step that replays one). Calls on
+ * the batch are serialised by the caller, as everywhere. */
+typedef struct {
+    uint64_t update_count, ssd_iters, sync_steps;
+    uint32_t env_call_count, reset_count;
+} pbn_batch_counters;
+int pbn_batch_get_counters(const pbn_batch *b, pbn_batch_counters *out);
+int pbn_batch_set_counters(pbn_batch *b, const pbn_batch_counters *in);
 /* Run every later call of this batch on `stream` (a hipStream_t, e.g. torch's current stream, so
  * kernels order with the caller's own work without host syncs; NULL = the default stream), or on
  * the batch's own stream again (own != 0). Work queued on the previous stream is waited for first. */

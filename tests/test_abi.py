@@ -91,6 +91,23 @@ def test_batch_create_validates_sizes_on_host():
     assert "n_envs" in _lib.last_error()
     assert _lib.lib.pbn_batch_create(net.handle, 0, 16, (1 << 56) - 8, 1, C.byref(h)) == _lib.PBN_E_RANGE
     assert _lib.lib.pbn_batch_create(None, 0, 16, 0, 1, C.byref(h)) == _lib.PBN_E_INVALID
+    # the range check holds where env_id_base + n_envs wraps in 64 bits, and at the first id past the field
+    for base, n in (((1 << 64) - 8, 16), (1 << 56, 1), ((1 << 64) - 1, 1)):
+        assert _lib.lib.pbn_batch_create(net.handle, 0, n, base, 1, C.byref(h)) == _lib.PBN_E_RANGE, (base, n)
+        assert "2^56" in _lib.last_error() and not h.value
+
+
+def test_batch_counters_refuse_null_arguments():
+    """pbn_batch_get_counters / pbn_batch_set_counters report NULL arguments like every entry point."""
+    import ctypes as C
+
+    from gym_pbn_amd import _lib
+
+    c = _lib.BatchCounters()
+    assert C.sizeof(c) == 32  # three uint64, two uint32: the header's struct, no padding
+    for f in (_lib.lib.pbn_batch_get_counters, _lib.lib.pbn_batch_set_counters):
+        assert f(None, C.byref(c)) == _lib.PBN_E_INVALID
+        assert _lib.last_error() == "batch is NULL"
 
 
 def test_every_host_file_reports_through_one_error_string():

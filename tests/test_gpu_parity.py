@@ -6,13 +6,13 @@ properties (shard invariance, step == rollout, sampled envs vs the oracle).
 """
 
 import os
-import zlib
 
 import numpy as np
 import pytest
 
 from conftest import cubes_to_attractors, golden, r6_config
 from gym_pbn_amd.network import load_network
+from r6_cases import ENV_VARIANT_CASES, env_variant_setup
 
 pytestmark = pytest.mark.gpu
 
@@ -806,84 +806,18 @@ def test_env_rollout_skips_invalid_action_steps(G, monkeypatch, group):
 
 
 # ----------------------------------------------------------------- env kernel variants vs the oracle
-def _random_cubes(rng, N, H, n_care):
-    cubes = []
-    for _ in range(H):
-        c = ["*"] * N
-        for j in rng.choice(N, size=n_care, replace=False):
-            c[int(j)] = int(rng.integers(0, 2))
-        cubes.append(tuple(c))
-    return cubes
-
-
-@pytest.mark.parametrize("case", ["b28_gen_cap", "b28_h8_gen", "b199_h6_gen_first_tested", "b28_h12_general",
-                                  "b199_nogen", "tt200_fast", "syn500_gen",
-                                  "syn300_wide_cube", "b28_first_tested", "b28_h12_first_tested",
-                                  "tt200_first_tested", "b199_grp2", "b199_grp4", "b199_grp8", "b28_grp4_cap",
-                                  "b28_grp8_first_tested", "b28_grp2_h8", "b199_grp4_long",
-                                  "b28_gen_cap41", "b199_gen_long", "b199_gen_long_first_tested",
-                                  "b28_gen_cap41_tail32", "b199_gen_long_tail32", "b199_gen_long_tail16",
-                                  "b199_gen_long_tail8", "b199_gen_long_tail1", "b199_gen_long_first_tested_tail32",
-                                  "b28_first_tested_tail32", "b28_gen_cap41_tail3", "b199_gen_long_tail0",
-                                  "b199_gen_long_lanes16", "b199_gen_long_lanes1", "b28_gen_cap41_lanes4",
-                                  "b199_gen_long_first_tested_lanes8"])
+@pytest.mark.parametrize("case", ENV_VARIANT_CASES)
 def test_env_kernel_variants_match_oracle(G, oracle_mod, monkeypatch, case):
     """Every k_env variant (cooperative draw generation, byte counters without it, general
     cube matching, truth-table kind, W = 8) against the oracle's R6 step, incl. capped envs and
     long until-attractor loops (thousands of updates per env step, odd caps). ``_tailK``: the
     cooperative-draw kernel's tail mode (a wave whose queue ran dry resolves its envs one at a time,
     64 updates per block) from K live envs per wave (32: early, many envs queued behind the one
-    resolved; 1: the last env only; 0: never; the default is ENV_TAIL_DEFAULT)."""
-    from gym_pbn_amd.network import PredictorNetwork, synthetic_predictor_sets
-
-    if "_tail" in case:  # the same inputs as the base case, another tail-mode threshold
-        monkeypatch.setenv("PBNSIM_ENV_TAIL", case.split("_tail")[1])
-        case = case.split("_tail")[0]
-    # lane mode proper (every lane takes envs) unless the case names K lanes per wave taking envs
-    # (tail mode from the first env; batches this small default to K = 1, DESIGN.md §6)
-    monkeypatch.setenv("PBNSIM_ENV_LANES", "64")
-    if "_lanes" in case:
-        monkeypatch.setenv("PBNSIM_ENV_LANES", case.split("_lanes")[1])
-        case = case.split("_lanes")[0]
-    rng = np.random.default_rng(zlib.crc32(case.encode()))
-    cap, A, B = 3000, 3, 1024
-    first = case.endswith("first_tested")  # PBNTargetEnv.step(force=False) semantics
-    # k_env_grp (G lanes per env, blocks of G updates resolved in parallel) or lane mode (1)
-    monkeypatch.setenv("PBNSIM_ENV_GROUP", case.split("_grp")[1][0] if "_grp" in case else "1")
-    if case.startswith("b199_grp") or case.startswith("b199_gen_long"):
-        net = load_network("bittner199")
-    elif case.startswith("b28"):
-        net = load_network("bittner28")
-    elif case == "b199_h6_gen_first_tested":
-        net = load_network("bittner199")
-    elif case == "b199_nogen":
-        net = load_network("bittner199")
-        monkeypatch.setenv("PBNSIM_ENV_NO_GEN", "1")
-    elif case.startswith("tt200"):
-        net = load_network("tt200")
-    else:
-        n = 500 if case == "syn500_gen" else 300
-        net = PredictorNetwork.from_predictor_sets(*synthetic_predictor_sets(n, 4, seed=n), name=f"syn{n}")
+    resolved; 1: the last env only; 0: never; the default is ENV_TAIL_DEFAULT). The case table and
+    its knobs: tests/r6_cases.py."""
+    c = env_variant_setup(case, monkeypatch)
+    case, net, attractors, cap, first, A, B, rng = c.case, c.net, c.attractors, c.cap, c.first, c.A, c.B, c.rng
     N = net.n_nodes
-    if case in ("b28_gen_cap", "b28_grp4_cap", "b28_gen_cap41"):
-        cap = 41 if ("grp" in case or "cap41" in case) else 40  # not a multiple of the group size
-        attractors = [_random_cubes(rng, N, 2, 5), _random_cubes(rng, N, 2, 5)]
-    elif case.startswith("b199_gen_long"):  # long loops: thousands of updates per env step
-        cap = 2001
-        attractors = [_random_cubes(rng, N, 2, 12), _random_cubes(rng, N, 2, 4)]
-    elif case == "b199_grp4_long":  # long until-attractor loops, many capped envs
-        cap = 2001
-        attractors = [_random_cubes(rng, N, 4, 12), _random_cubes(rng, N, 2, 4)]
-    elif case in ("b28_grp2_h8", "b28_h8_gen"):  # 8 cubes: the most the byte counters hold
-        attractors = [_random_cubes(rng, N, 4, 4), _random_cubes(rng, N, 4, 4)]
-    elif case == "b199_h6_gen_first_tested":  # 5..8 cubes: both packed counter words
-        attractors = [_random_cubes(rng, N, 3, 3), _random_cubes(rng, N, 3, 3)]
-    elif case.startswith("b28_h12"):
-        attractors = [_random_cubes(rng, N, 6, 4), _random_cubes(rng, N, 6, 4)]
-    elif case == "syn300_wide_cube":  # one cube caring about 260 > 255 nodes: general matching
-        attractors = [_random_cubes(rng, N, 1, 260) + _random_cubes(rng, N, 2, 3), _random_cubes(rng, N, 1, 3)]
-    else:
-        attractors = [_random_cubes(rng, N, 2, 4), _random_cubes(rng, N, 2, 4)]
     gnet = G.Net(net)
     cfg = G.EnvConfig(gnet, attractors, horizon=3, first_update_tested=first)
     o = oracle_mod.Oracle(net)

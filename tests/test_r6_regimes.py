@@ -21,6 +21,7 @@ import pytest
 
 from conftest import cubes_to_attractors, golden, r6_config
 from gym_pbn_amd.network import load_network
+from r6_cases import FORCED_TAIL_CASES, forced_tail_knobs, long_first_step_actions
 
 pytestmark = pytest.mark.gpu
 
@@ -435,7 +436,7 @@ def test_tail_handoff_between_waves_matches_oracle(G, oracle_mod, monkeypatch, m
     b.close()
 
 
-@pytest.mark.parametrize("case", ["handoff", "helpers", "helpers_off", "grid", "grid_off"])
+@pytest.mark.parametrize("case", FORCED_TAIL_CASES)
 @pytest.mark.parametrize("mode", ["per_step", "fused"])
 def test_tail_handoff_forced_happens_and_matches_oracle(G, oracle_mod, monkeypatch, mode, case):
     """A case in which the workgroup hand-off must happen: one workgroup (4 waves), two
@@ -460,12 +461,7 @@ def test_tail_handoff_forced_happens_and_matches_oracle(G, oracle_mod, monkeypat
     import torch
 
     grid_case = case.startswith("grid")
-    monkeypatch.setenv("PBNSIM_ENV_LANES", "16" if grid_case else "2")
-    monkeypatch.setenv("PBNSIM_ENV_GRID", "2" if grid_case else "1")
-    if case == "helpers_off":
-        monkeypatch.setenv("PBNSIM_ENV_HELPERS", "0")
-    if case == "grid_off":
-        monkeypatch.setenv("PBNSIM_ENV_GRID_STEAL", "0")
+    B = forced_tail_knobs(case, monkeypatch)
     import sys
     from pathlib import Path
 
@@ -479,23 +475,11 @@ def test_tail_handoff_forced_happens_and_matches_oracle(G, oracle_mod, monkeypat
     cfgd = dict(care=cfg.cube_care, value=cfg.cube_value, target_care=cfg.target_care, target_value=cfg.target_value,
                 horizon=100)
     o = oracle_mod.Oracle(net)
-    B = {"handoff": 6, "grid": 16, "grid_off": 16}.get(case, 2)
     seed, base, T, A, cap = 0xAC7, 90001, 2, 4, bench.R6_HIGH_CAP
     st, ns = o.env_reset_philox(np.zeros((B, net.n_words), np.uint64), np.ones(B, np.int64), cfg.reset_care,
                                 cfg.reset_value, seed=seed, env_base=base, reset_count=0)
     # per env, the first candidate action row (oracle) whose first env step runs >= 2,048 updates
-    acts = _actions(np.random.default_rng(77), (T, B, A), net.n_nodes)
-    rng = np.random.default_rng(78)
-    need = np.ones(B, bool)
-    for _ in range(400):
-        cand = _actions(rng, (B, A), net.n_nodes)
-        r = o.env_step_multi(cfgd, st, ns, cand, seed=seed, env_base=base, call_idx=0, update_cap=cap)
-        ok = need & (r["n_updates"] >= 2048)
-        acts[0][ok] = cand[ok]
-        need &= ~ok
-        if not need.any():
-            break
-    assert not need.any()
+    acts = long_first_step_actions(o, cfgd, st, ns, net.n_nodes, (T, B, A), seed, base, cap)
     b = G.PBNBatch(gnet, B, seed=seed, env_id_base=base)
     b.env_reset(cfg)
     st, ns = o.env_reset_philox(np.zeros((B, net.n_words), np.uint64), np.ones(B, np.int64), cfg.reset_care,
