@@ -35,7 +35,7 @@ void DevCache::release() {
 // The PBNSIM_* launch knobs (measurement / tests), read once per batch.
 static Knobs read_knobs() {
     Knobs k;
-    if (const char* sm = getenv("PBNSIM_STORE_MODE")) k.store_mode = atoi(sm) ? STORE_DIRTY : STORE_FULL;
+    if (const char* sm = getenv("PBNSIM_STORE_MODE")) k.store_mode = std::max(0, std::min(2, atoi(sm)));
     if (const char* r = getenv("PBNSIM_ENVS_PER_THREAD")) k.envs_per_thread = std::max(1, std::min(64, atoi(r)));
     if (const char* v = getenv("PBNSIM_STEP_BLOCK")) k.step_block = atoi(v) == 256 ? 256 : 1024;
     k.env.no_gen = getenv("PBNSIM_ENV_NO_GEN") != nullptr;

@@ -49,7 +49,11 @@ static int step_launch(pbn_batch* b, const StepRange& r, const StepWork& w) {
     hipEvent_t stop = nullptr;
     if (timed)
         if (int rc = b->ev_begin(&stop)) return rc;
-    int store = (T == 1 && !replay) ? b->knob.store_mode : STORE_FULL;
+    int store = STORE_FULL;
+    if (T == 1 && !replay) {  // PBNSIM_STORE_MODE forces the write-back; by size otherwise (step_half_store)
+        store = step_half_store(b->B, b->n_cu, b->step.block) ? STORE_HALF : STORE_DIRTY;
+        if (b->knob.store_mode >= 0) store = b->knob.store_mode;
+    }
     // step mode: K envs per thread (their loads overlap); rollout: one env per lane up to the
     // resident grid -- its T updates are the work, and more lanes hide more LDS latency
     // (Bittner-28 @65,536 envs, T = 256: 115 vs 62 G updates/s with K = 2)

@@ -158,6 +158,32 @@ __device__ __forceinline__ void store_state(uint64_t* __restrict__ p, const uint
     }
 }
 
+// Write-back of an env whose node i (< 64W) changed: the env with bit i flipped. HALF, W even and >= 4:
+// only the 16-B granule g = i >> 7 that holds the bit, its two words taken by static selects over the
+// unrolled words (no register indexing) and written by ONE 16-B store whose address varies by lane
+// (not a pair of exec-masked stores). Otherwise (W == 2: the env is the granule) the whole env.
+template <int W, bool HALF>
+__device__ __forceinline__ void store_changed(uint64_t* __restrict__ env, const uint64_t (&s)[W], uint32_t i) {
+    const uint64_t m = 1ull << (i & 63u);
+    if constexpr (HALF && W % 2 == 0 && W >= 4) {
+        const uint32_t g = i >> 7;
+        uint64_t lo = s[0], hi = s[1];
+#pragma unroll
+        for (int k = 1; k < W / 2; ++k) {
+            lo = g == (uint32_t)k ? s[2 * k] : lo;
+            hi = g == (uint32_t)k ? s[2 * k + 1] : hi;
+        }
+        const bool up = (i & 64u) != 0u;  // the bit is in the granule's second word
+        *reinterpret_cast<ulonglong2*>(env + 2u * g) = make_ulonglong2(lo ^ (up ? 0ull : m), hi ^ (up ? m : 0ull));
+    } else {
+        uint64_t out[W];
+        const uint32_t wi = i >> 6;
+#pragma unroll
+        for (int k = 0; k < W; ++k) out[k] = s[k] ^ ((uint32_t)k == wi ? m : 0ull);
+        store_state<W>(env, out);
+    }
+}
+
 // ---------------------------------------------------------------- LDS staging
 // Copy the network image (16-byte granules) into LDS; every thread participates.
 __device__ __forceinline__ void stage_image(const uint4* __restrict__ img, uint32_t n16, uint4* lds) {

@@ -156,7 +156,7 @@ inline int check_action_shape(int A, int offset) {
 
 // Launch knobs read from PBNSIM_* once at pbn_batch_create (read_knobs, pbn_abi.cpp): measurement / tests.
 struct Knobs {
-    int store_mode = STORE_DIRTY;  // PBNSIM_STORE_MODE
+    int store_mode = -1;           // PBNSIM_STORE_MODE: 0 full, 1 changed envs whole, 2 their changed 16-B half, -1 = by size
     int envs_per_thread = 2;       // PBNSIM_ENVS_PER_THREAD: K, envs each thread walks per launch (pipelined)
     int step_block = 0;            // PBNSIM_STEP_BLOCK: 256 / 1024 threads per workgroup of the step kernel, 0 = by size
     int step_graph = -1;           // PBNSIM_STEP_GRAPH=0/1 forces step mode without / with HIP graphs, -1 = by size

@@ -15,7 +15,9 @@ enum {
     STREAM_SYNC = 7,
     STREAM_SYNC_PERT = 8
 };
-enum { STORE_FULL = 0, STORE_DIRTY = 1 };
+// STORE_DIRTY / STORE_HALF write back the envs whose updated bit changed: the whole env, or (W even and >= 4,
+// 1024-thread step kernels) only the 16-B half that holds the bit (store_changed, pbn_device.hpp)
+enum { STORE_FULL = 0, STORE_DIRTY = 1, STORE_HALF = 2 };
 // R6 env-step modes: EnvArgs::mode, EnvPlan::mode and k_env's template parameter
 enum EnvMode {
     ENV_MODE_CUBES = 0,     // the state matched against every cube after a change

@@ -116,7 +116,7 @@ __device__ __forceinline__ void k_step_single(const StepArgs& a, uint8_t* lds, u
             st[3] = __builtin_amdgcn_s_memrealtime();
         }
 #endif
-        if constexpr (STORE == STORE_DIRTY) {
+        if constexpr (STORE != STORE_FULL) {
             // Both envs evaluated first (plane writes and reads of env 1 issued right behind env 0's;
             // LDS runs a wave's operations in order, so reusing the column needs no wait), then both
             // stores: with env 0's store issued before env 1's loads were consumed, the compiler
@@ -141,18 +141,15 @@ __device__ __forceinline__ void k_step_single(const StepArgs& a, uint8_t* lds, u
             uint32_t self0, self1;
             const uint32_t y0 = eval(cur, i0, r0, q0, self0);
             const uint32_t y1 = eval(nxt, i1, r1, q1, self1);
-            // store the whole env (32 B at W = 4), and only if its bit changed: a full aligned env
-            // write measured faster than writing just the 16-B half that holds node i (7.69 vs
-            // 7.93 us at 1M envs), partial sector writes cost extra. The env's words are still in
-            // registers: bit i is flipped there (one 64-bit select per word) rather than written to
-            // the plane and all 2W dwords read back
+            // An env is stored only if its bit changed: whole (STORE_DIRTY, 32 B at W = 4) or, STORE_HALF,
+            // just the 16-B half that holds node i. Which one is the host's choice by batch size
+            // (step_half_store, pbn_step_plan.hpp): the half store wins while the whole batch is resident
+            // at once (1M Bittner-200 envs: 9.5 -> 8.8 us per step) and loses from 2M envs on, where
+            // half-written 32-B sectors cost more than the bytes saved (8M: 55.5 -> 59.2 us). The env's
+            // words are still in registers: bit i is flipped there (store_changed) rather than written
+            // to the plane and all 2W dwords read back
             auto put = [&](const uint64_t (&s)[W], uint64_t eh, uint32_t i) {
-                uint64_t out[W];
-                const uint32_t wi = i >> 6;
-                const uint64_t m = 1ull << (i & 63u);
-#pragma unroll
-                for (int k = 0; k < W; ++k) out[k] = s[k] ^ ((uint32_t)k == wi ? m : 0ull);
-                store_state<W>(a.state + eh * W, out);
+                store_changed<W, STORE == STORE_HALF>(a.state + eh * W, s, i);
             };
             if (((self0 >> (i0 & 31u)) & 1u) != y0) put(cur, e, i0);
             if (e1 < a.B && ((self1 >> (i1 & 31u)) & 1u) != y1) put(nxt, e1, i1);
@@ -205,7 +202,7 @@ __device__ __forceinline__ void k_step_single(const StepArgs& a, uint8_t* lds, u
 // and both records in a second (the looped form read env 0's row, its record, env 1's row, its
 // record: three dependent round trips, the uniform tp4 == 4 branch between them), and env 0's plane
 // work waits only for env 0's loads.
-template <int W, int SB>
+template <int W, int STORE, int SB>
 __device__ __forceinline__ void k_step_pair(const StepArgs& a, uint8_t* lds, uint64_t e, uint64_t stride,
                                             const uint64_t (&cur)[W], const uint64_t (&nxt)[W], uint32_t N) {
     const uint64_t u = a.update_base + (a.ubase_dev ? *a.ubase_dev : 0ull);
@@ -242,13 +239,8 @@ __device__ __forceinline__ void k_step_pair(const StepArgs& a, uint8_t* lds, uin
         self = P.get(i >> 5);
         return predictor_apply(P, i, self, r);
     };
-    auto put = [&](const uint64_t (&s)[W], uint64_t eh, uint32_t i) {  // whole env, bit i flipped
-        uint64_t out[W];
-        const uint32_t wi = i >> 6;
-        const uint64_t m = 1ull << (i & 63u);
-#pragma unroll
-        for (int k = 0; k < W; ++k) out[k] = s[k] ^ ((uint32_t)k == wi ? m : 0ull);
-        store_state<W>(a.state + eh * W, out);
+    auto put = [&](const uint64_t (&s)[W], uint64_t eh, uint32_t i) {  // bit i flipped (store_changed)
+        store_changed<W, STORE == STORE_HALF>(a.state + eh * W, s, i);
     };
     uint32_t self0, self1;
     const uint32_t y0 = eval(cur, i0, r0, self0);
@@ -295,8 +287,8 @@ void k_step(StepArgs a) {
         if (threadIdx.x < n16) reinterpret_cast<uint4*>(lds)[threadIdx.x] = g;
         for (uint32_t k = threadIdx.x + SB; k < n16; k += SB) reinterpret_cast<uint4*>(lds)[k] = src[k];
         __syncthreads();
-        if (STORE == STORE_DIRTY && 2u * stride >= a.B)
-            k_step_pair<W, SB>(a, lds, e, stride, cur, nx, N);  // one pair per thread (the bench shape)
+        if (STORE != STORE_FULL && 2u * stride >= a.B)
+            k_step_pair<W, STORE, SB>(a, lds, e, stride, cur, nx, N);  // one pair per thread (the bench shape)
         else
             k_step_single<W, KIND, STORE, SB, true>(a, lds, e, stride, cur, N, &nx);
         return;
@@ -449,6 +441,10 @@ static void* step_fn(int store, int replay, int sb, int rollout, int grp) {
     if (replay) return (void*)k_step<W, KIND, STORE_FULL, 1, BLOCK>;
     if (grp > 1) return rollout && KIND == KIND_PREDICTOR_MIX ? rollout_grp_kernel(W, grp) : nullptr;
     if (rollout) return sb == 1024 ? (void*)k_rollout<W, KIND, 1024> : (void*)k_rollout<W, KIND, BLOCK>;
+    if (sb != 1024 && store == STORE_HALF) store = STORE_DIRTY;  // the half store: 1024-thread kernels only
+    if constexpr (W % 2 == 0 && W >= 4)
+        if (store == STORE_HALF) return (void*)k_step<W, KIND, STORE_HALF, 0, 1024>;
+    if (store == STORE_HALF) store = STORE_DIRTY;  // W odd or < 4: the whole env is the write-back
     if (sb == 1024)
         return store == STORE_DIRTY ? (void*)k_step<W, KIND, STORE_DIRTY, 0, 1024>
                                     : (void*)k_step<W, KIND, STORE_FULL, 0, 1024>;

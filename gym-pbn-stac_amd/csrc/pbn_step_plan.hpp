@@ -63,6 +63,18 @@ inline StepShape step_shape(uint64_t B, int W, int n_cu, int step_block, int ste
     return s;
 }
 
+// The dirty write-back of the 1024-thread step kernels (STORE_HALF against STORE_DIRTY, pbn_params.hpp) by size:
+// only the changed 16-B half of an env while the whole batch is resident at once -- two 1024-thread workgroups
+// per CU, one env pair per thread, so n_cu x 4096 envs: the launch is one round of workgroups, it ends with its
+// slowest wave, and one store instruction per env instead of two shortens that (1M Bittner-200 envs on 256 CUs,
+// plain launches: 9.54 -> 8.83 us per step; 512K envs 5.25 -> 5.19). A larger batch keeps workgroups queued behind the resident ones and
+// runs at the rate of its memory traffic, where a half-written 32-B sector costs more than a whole one (2M envs
+// 14.6 -> 15.7 us per step with the half store, 4M 27.9 -> 29.7, 8M 55.5 -> 59.2): the whole env there.
+// profiles/step_half_store_ab.json
+inline bool step_half_store(uint64_t B, int n_cu, int block) {
+    return block == 1024 && B <= (uint64_t)n_cu * 4096u;
+}
+
 // One pbn_step call (pbn_step_prepare: the call it prepares).
 struct StepCall {
     // two or more updates, no event pair per launch (timing mode 1), not inside the caller's capture of the

@@ -15,9 +15,12 @@
 
 namespace {
 
-__global__ __launch_bounds__(1024) void k_probe(uint64_t* __restrict__ s, uint64_t B, uint32_t write_pct,
-                                                uint32_t passes, uint64_t* __restrict__ sink, uint32_t salt,
-                                                uint32_t glog, uint32_t wbytes) {
+// LANE16: the 16-B form is one store at a lane-varying address (an instance of its own, so the existing
+// entry points keep the code they were measured with)
+template <bool LANE16>
+__global__ __launch_bounds__(1024) void k_probe_t(uint64_t* __restrict__ s, uint64_t B, uint32_t write_pct,
+                                                  uint32_t passes, uint64_t* __restrict__ sink, uint32_t salt,
+                                                  uint32_t glog, uint32_t wbytes) {
     const uint64_t stride = (uint64_t)gridDim.x * 1024u;
     uint64_t acc = 0;
     for (uint32_t p = 0; p < passes; ++p) {
@@ -46,7 +49,10 @@ __global__ __launch_bounds__(1024) void k_probe(uint64_t* __restrict__ s, uint64
                     return;
                 }
                 const uint32_t wsel = (uint32_t)(e * 0x9E3779B9u) >> 30;
-                if (wbytes == 16u) {
+                if (LANE16 && wbytes == 16u) {  // the kernel's store_changed: one store, the half chosen by address
+                    const bool up = (wsel >> 1) != 0u;
+                    q[up ? 1 : 0] = make_ulonglong2(up ? v1.x : v0.x, up ? v1.y : v0.y);
+                } else if (wbytes == 16u) {
                     if (wsel >> 1)
                         q[1] = v1;
                     else
@@ -78,7 +84,7 @@ __global__ __launch_bounds__(1024) void k_probe(uint64_t* __restrict__ s, uint64
 // fraction, `passes` passes per launch and `launches` timed launches (after 3 untimed ones).
 // Returns 0 on success, a HIP error code otherwise.
 static int probe_impl(uint64_t n_envs, int write_pct, int passes, int launches, int vary, int glog,
-                      double* us_per_pass, int wbytes = 32) {
+                      double* us_per_pass, int wbytes = 32, bool lane16 = false) {
     if (!us_per_pass || n_envs < 2048 || passes < 1 || launches < 1) return -1;
     int dev = 0, n_cu = 0;
     if (hipGetDevice(&dev) != hipSuccess) return -2;
@@ -94,6 +100,7 @@ static int probe_impl(uint64_t n_envs, int write_pct, int passes, int launches, 
     const uint64_t pairs = (n_envs + 1) / 2;
     const uint64_t want = (pairs + 1023) / 1024;
     const int grid = (int)(want < (uint64_t)n_cu * 2u ? want : (uint64_t)n_cu * 2u);
+    const auto k_probe = lane16 ? k_probe_t<true> : k_probe_t<false>;
     if (e == hipSuccess) {
         for (int w = 0; w < 3; ++w) hipLaunchKernelGGL(k_probe, dim3(grid), dim3(1024), 0, 0, s, n_envs,
                                                        (uint32_t)write_pct, (uint32_t)passes, sink,
@@ -138,4 +145,10 @@ extern "C" int mall_probe_group(uint64_t n_envs, int write_pct, int glog, int la
 extern "C" int mall_probe_wbytes(uint64_t n_envs, int write_pct, int wbytes, int launches, double* us_per_pass) {
     if (wbytes != 8 && wbytes != 16 && wbytes != 32) return -1;
     return probe_impl(n_envs, write_pct, 1, launches, 1, 0, us_per_pass, wbytes);
+}
+
+// The 16-B half of each written env as ONE store whose address varies by lane (the step kernel's
+// store_changed); mall_probe_wbytes' 16-B form is two exec-masked stores.
+extern "C" int mall_probe_half16(uint64_t n_envs, int write_pct, int launches, double* us_per_pass) {
+    return probe_impl(n_envs, write_pct, 1, launches, 1, 0, us_per_pass, 16, true);
 }
