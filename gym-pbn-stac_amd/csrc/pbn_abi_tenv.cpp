@@ -1,0 +1,176 @@
+// pbn_abi_tenv.cpp -- exact state sets (pbn_stateset_*) and the PBN-v0 env on the device (pbn_tenv_*): the
+// entry points over pbn_stateset.hpp (the set's one definition) and the kernels of pbn_tenv.hip.
+#include "pbn_host.hpp"
+
+// The set can serve this batch's launches: uploaded, on the batch's device, over states of the batch's width.
+static int check_set_for_batch(const pbn_batch* b, const pbn_stateset* s, const char* what) {
+    if (s->device < 0) return fail(PBN_E_STATE, "%s is a host-only state set (created with device -1)", what);
+    if (s->device != b->device)
+        return fail(PBN_E_INVALID, "%s lives on device %d, the batch on device %d", what, s->device, b->device);
+    if (s->t.n_nodes != b->N)
+        return fail(PBN_E_INVALID, "%s holds states of %d nodes, the batch has %d", what, s->t.n_nodes, b->N);
+    return 0;
+}
+
+static int check_table_batch(const pbn_batch* b, const char* fn) {
+    if (b->net->kind != PBN_KIND_PROB_TABLE)
+        return fail(PBN_E_UNSUPPORTED, "%s steps the PBN-v0 env of a truth-table network; this batch holds a "
+                                       "predictor-mix network (its env is pbn_env_step_multi)", fn);
+    return 0;
+}
+
+extern "C" {
+
+int pbn_stateset_create(int32_t n_nodes, int device, const uint64_t* states, const int32_t* labels, uint64_t n_states,
+                        pbn_stateset** out) {
+    CHECK_NN(out, "out");
+    *out = nullptr;
+    if (n_states && !states) return fail(PBN_E_INVALID, "states is NULL");
+    if (n_nodes < 1 || n_nodes > 64 * MAX_WORDS)
+        return fail(PBN_E_INVALID, "n_nodes=%d outside [1, %d]", (int)n_nodes, 64 * MAX_WORDS);
+    if (n_states > PBN_STATESET_MAX_STATES)
+        return fail(PBN_E_INVALID, "n_states=%llu above PBN_STATESET_MAX_STATES (%llu)", (unsigned long long)n_states,
+                    (unsigned long long)PBN_STATESET_MAX_STATES);
+    if (device < -1) return fail(PBN_E_RANGE, "device %d: a device index, or -1 for a host-only set", device);
+    pbn_stateset* s = new pbn_stateset;
+    uint64_t row = 0;
+    switch (stateset_build(n_nodes, states, labels, n_states, &s->t, &row)) {
+        case STATESET_OK: break;
+        case STATESET_E_STRAY_BITS:
+            delete s;
+            return fail(PBN_E_INVALID, "state %llu has bits set beyond node %d", (unsigned long long)row, n_nodes - 1);
+        case STATESET_E_LABEL:
+            delete s;
+            return fail(PBN_E_INVALID, "state %llu has a negative label", (unsigned long long)row);
+        case STATESET_E_CONFLICT:
+            delete s;
+            return fail(PBN_E_INVALID, "state %llu repeats an earlier state under a different label",
+                        (unsigned long long)row);
+        default:
+            delete s;
+            return fail(PBN_E_INVALID, "state set shape refused");
+    }
+    if (device >= 0) {
+        auto bail = [&](int code) {
+            pbn_stateset_destroy(s);
+            return code;
+        };
+        if (int rc = open_device(device)) {
+            delete s;
+            return rc;
+        }
+        s->device = device;
+        const size_t mb = 4 * (size_t)s->t.slots, kb = 8 * (size_t)s->t.W * s->t.slots;
+        if (int rc = s->meta.ensure(mb)) return bail(rc);
+        if (int rc = s->keys.ensure(kb)) return bail(rc);
+        if (hipMemcpy(s->meta.p, s->t.meta.data(), mb, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(s->keys.p, s->t.keys.data(), kb, hipMemcpyHostToDevice) != hipSuccess)
+            return bail(fail(PBN_E_HIP, "state set upload failed"));
+    }
+    *out = s;
+    return 0;
+}
+
+void pbn_stateset_destroy(pbn_stateset* s) {
+    if (!s) return;
+    if (s->device >= 0) (void)hipSetDevice(s->device);
+    delete s;  // the DevBufs give back the device copy
+}
+
+int pbn_stateset_get_info(const pbn_stateset* s, pbn_stateset_info* info) {
+    CHECK_NN(s, "stateset");
+    CHECK_NN(info, "info");
+    info->n_nodes = s->t.n_nodes;
+    info->n_words = s->t.W;
+    info->device = s->device;
+    info->n_states = s->t.n_states;
+    info->table_slots = s->t.slots;
+    info->max_probe = s->t.max_probe;
+    return 0;
+}
+
+int pbn_stateset_lookup(const pbn_stateset* s, const uint64_t* states, uint64_t n, int32_t* labels) {
+    CHECK_NN(s, "stateset");
+    if (!n) return 0;
+    CHECK_NN(states, "states");
+    CHECK_NN(labels, "labels");
+    stateset_lookup_host(s->t, states, n, labels);
+    return 0;
+}
+
+int pbn_stateset_lookup_device(pbn_batch* b, const pbn_stateset* s, const void* d_words, int32_t* d_labels) {
+    CHECK_NN(b, "batch");
+    CHECK_NN(s, "stateset");
+    CHECK_NN(d_labels, "d_labels");
+    if (int rc = check_set_for_batch(b, s, "the state set")) return rc;
+    SET_DEV(b);
+    SetLookupArgs a{d_words ? (const uint64_t*)d_words : b->d_state, s->view(), b->B, d_labels};
+    return timed_launch(b, "k_set_lookup", [&] { return launch_set_lookup(b->W, a, b->stream); });
+}
+
+int pbn_tenv_step_device(pbn_batch* b, const pbn_stateset* target, const int32_t* d_actions, int32_t reward_target,
+                         int32_t step_cost, int32_t action_cost, int check, uint64_t* d_obs, int32_t* d_reward,
+                         uint8_t* d_flags, int32_t* d_labels) {
+    CHECK_NN(b, "batch");
+    CHECK_NN(target, "target");
+    CHECK_NN(d_actions, "d_actions");
+    CHECK_NN(d_reward, "d_reward");
+    CHECK_NN(d_flags, "d_flags");
+    if (int rc = check_table_batch(b, "pbn_tenv_step_device")) return rc;
+    if (int rc = check_set_for_batch(b, target, "the target set")) return rc;
+    if (b->N < 2) return fail(PBN_E_UNSUPPORTED, "PBN.step updates a node in [1, N-1]: the network needs two nodes");
+    SET_DEV(b);
+    int32_t* flag = (int32_t*)b->tenv.err.p;  // zeroed at allocation and after every check
+    if (!flag) {
+        if (int rc = b->tenv.err.ensure(4)) return rc;
+        flag = (int32_t*)b->tenv.err.p;
+        HIP_TRY(hipMemsetAsync(flag, 0, 4, b->stream));
+    }
+    if (!b->tenv.bpc)
+        if (int e = max_blocks_tenv(b->W, b->net->L.plane_off, &b->tenv.bpc))
+            return fail(PBN_E_HIP, "occupancy query: %s", hipGetErrorString((hipError_t)e));
+    TenvArgs a{};
+    a.state = b->d_state;
+    a.img = b->d_image;
+    a.L = b->net->L;
+    a.B = b->B;
+    a.env_base = b->env_base;
+    a.seed = b->seed;
+    a.update = b->update_count;
+    a.actions = d_actions;
+    a.target = target->view();
+    a.reward_target = reward_target;
+    a.step_cost = step_cost;
+    a.action_cost = action_cost;
+    a.obs = d_obs;
+    a.reward = d_reward;
+    a.flags = d_flags;
+    a.labels = d_labels;
+    a.error = flag;
+    const int grid = b->grid_for(b->B, b->tenv.bpc);
+    if (int rc = timed_launch(b, "k_tenv_step", [&] { return launch_tenv_step(b->W, a, grid, b->stream); })) return rc;
+    b->update_count++;  // the launch happened: the count advances whether or not an action was refused
+    if (!check) return 0;
+    if (!b->pin.ready()) return fail(PBN_E_NOMEM, "pinned staging buffer");
+    HIP_TRY(hipMemcpyAsync(b->pin.p, flag, 4, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipMemsetAsync(flag, 0, 4, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    int32_t err;
+    memcpy(&err, b->pin.p, 4);
+    if (err) return fail(PBN_E_RANGE, "Invalid action: a value outside [0, %d] (envs holding one were left untouched)", b->N - 1);
+    return 0;
+}
+
+int pbn_tenv_reset_device(pbn_batch* b, const uint64_t* d_states, uint64_t n_states, const uint8_t* d_mask) {
+    CHECK_NN(b, "batch");
+    CHECK_NN(d_states, "d_states");
+    if (int rc = check_table_batch(b, "pbn_tenv_reset_device")) return rc;
+    if (n_states == 0 || n_states >> 32) return fail(PBN_E_INVALID, "n_states outside [1, 2^32)");
+    SET_DEV(b);
+    TenvResetArgs a{b->d_state, b->B, b->env_base, b->seed, b->reset_count, d_states, (uint32_t)n_states, d_mask};
+    if (int rc = timed_launch(b, "k_tenv_reset", [&] { return launch_tenv_reset(b->W, a, b->stream); })) return rc;
+    b->reset_count++;
+    return 0;
+}
+
+}  // extern "C"

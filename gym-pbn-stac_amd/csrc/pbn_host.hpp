@@ -21,6 +21,7 @@
 #include "pbn_env_plan.hpp"
 #include "pbn_step_plan.hpp"
 #include "pbn_reach_rule.hpp"
+#include "pbn_stateset.hpp"
 
 using namespace pbn;
 
@@ -255,6 +256,10 @@ struct pbn_batch {
         DevBuf sync_tab;           // perturbation gap table
         uint64_t sync_steps = 0;   // synchronous-step counter (Philox)
     } aux;
+    struct Tenv {        // the PBN-v0 env on the device (pbn_abi_tenv.cpp)
+        DevBuf err;      // sticky range flag of pbn_tenv_step_device, zeroed at allocation and after every check
+        int bpc = 0;     // k_tenv_step's resident workgroups per CU (0: not asked yet)
+    } tenv;
     // timing: mode 1 = an event pair around every launch; mode 2 = one region
     // (start before the first launch after enabling, stop after the latest launch)
     struct Timing {
@@ -329,6 +334,15 @@ inline int timed_launch(pbn_batch* b, const char* kernel, F&& launch) {
 PBN_HIDDEN int validate_actions(const pbn_batch* b, const int32_t* actions, int A, int offset);
 PBN_HIDDEN int h2d(pbn_batch* b, void* dst, const void* src, size_t bytes);
 PBN_HIDDEN int run_init(pbn_batch* b, const pbn_envcfg* cfg, const void* d_mask, const void* care, const void* value);
+
+// An exact set of packed states (pbn_stateset.hpp): the host copy, and with device >= 0 its upload. Read-only once
+// built. Entry points in pbn_abi_tenv.cpp.
+struct pbn_stateset {
+    int device = -1;  // -1: host copy only
+    StateSetTable t;
+    DevBuf meta, keys;  // given back by the destructor (pbn_stateset_destroy makes the device current)
+    SetView view() const { return SetView{(const uint32_t*)meta.p, (const uint64_t*)keys.p, t.slots}; }
+};
 
 // Attractor discovery (pbn_reach.hip); entry points in pbn_abi_reach.cpp.
 struct pbn_reach {

@@ -13,7 +13,8 @@ enum {
     STREAM_SSD = 5,
     STREAM_SSD_FLIP = 6,
     STREAM_SYNC = 7,
-    STREAM_SYNC_PERT = 8
+    STREAM_SYNC_PERT = 8,
+    STREAM_TENV_RESET = 9  // pbn_tenv_reset_device: ctr {0, reset_count, env id}, row = mulhi(w[0], n_states)
 };
 // STORE_DIRTY / STORE_HALF write back the envs whose updated bit changed: the whole env, or (W even and >= 4,
 // 1024-thread step kernels) only the 16-B half that holds the bit (store_changed, pbn_device.hpp)
@@ -345,9 +346,53 @@ struct ReachArgs {
     uint32_t epoch;
 };
 
+// The PBN-v0 env on the device (pbn_tenv.hip): an exact state set a kernel can query
+// (pbn_stateset.hpp), the fused step and the reset over a table of states.
+struct SetView {
+    const uint32_t* meta;  // [slots] 0 = empty, else label + 1
+    const uint64_t* keys;  // [slots][W]
+    uint32_t slots;        // a power of two
+};
+
+struct SetLookupArgs {
+    const uint64_t* words;  // [B][W]: the batch's state or the caller's words
+    SetView set;
+    uint64_t B;
+    int32_t* labels;  // [B]
+};
+
+struct TenvArgs {
+    uint64_t* state;         // [B][W]
+    const void* img;         // truth-table network image
+    NetLayout L;
+    uint64_t B, env_base, seed;
+    uint64_t update;         // the batch's update counter: this step is update `update` of every env
+    const int32_t* actions;  // [B]: 0 = none, a in [1, N-1] flips node a
+    SetView target;
+    int32_t reward_target, step_cost, action_cost;
+    uint64_t* obs;           // [B][W] or null
+    int32_t* reward;         // [B]
+    uint8_t* flags;          // [B]
+    int32_t* labels;         // [B] or null
+    int32_t* error;          // sticky: set to 1 by an env whose action names no node (the env is skipped)
+};
+
+struct TenvResetArgs {
+    uint64_t* state;
+    uint64_t B, env_base, seed;
+    uint32_t reset_count;
+    const uint64_t* states;  // [n_states][W]
+    uint32_t n_states;       // >= 1
+    const uint8_t* mask;     // [B] or null
+};
+
 // Launchers (pbn_step.hip, pbn_state.hip, pbn_env.hip, pbn_group.hip, pbn_mt.hip, pbn_ssd.hip, pbn_sync.hip, pbn_reach.hip). Return hipError_t as int.
 enum { REACH_K_UNSTABLE = 0, REACH_K_SEED, REACH_K_EXPAND, REACH_K_BACK_START, REACH_K_BACK, REACH_K_HULL };
 int launch_reach(int W, int which, const ReachArgs& a, int grid, void* stream);
+int launch_set_lookup(int W, const SetLookupArgs& a, void* stream);
+int launch_tenv_step(int W, const TenvArgs& a, int grid, void* stream);
+int launch_tenv_reset(int W, const TenvResetArgs& a, void* stream);
+int max_blocks_tenv(int W, uint32_t image_bytes, int* blocks_per_cu);
 int launch_bump(uint64_t* p, uint64_t k, void* stream);
 int launch_set_counters(uint64_t* p, uint64_t v, uint32_t n, void* stream);
 int launch_step(int W, const StepArgs& a, int store_mode, int replay, int sb, int grid, void* stream);

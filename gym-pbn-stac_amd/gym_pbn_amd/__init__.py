@@ -26,7 +26,8 @@ def __getattr__(name):
         from . import batch
 
         return getattr(batch, name)
-    if name in ("Graph", "PBN", "PBNTargetEnv", "PBNTargetMultiEnv", "VecPBNTargetMultiEnv", "PBNEnv", "state_to_idx"):
+    if name in ("Graph", "PBN", "PBNTargetEnv", "PBNTargetMultiEnv", "VecPBNTargetMultiEnv", "VecPBNEnv", "PBNEnv",
+                "state_to_idx"):
         from . import envs
 
         return getattr(envs, name)
@@ -34,6 +35,14 @@ def __getattr__(name):
         from . import attractors
 
         return getattr(attractors, name)
+    if name == "StateSet":
+        from .stateset import StateSet
+
+        return StateSet
+    if name in ("TorchVecPBNEnv", "TorchVecPBNTargetMultiEnv"):
+        from . import torch_env
+
+        return getattr(torch_env, name)
     if name == "make":
         from .registry import make
 

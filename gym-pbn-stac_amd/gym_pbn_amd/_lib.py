@@ -98,6 +98,15 @@ class ReachInfo(C.Structure):
     ]
 
 
+class StateSetInfo(C.Structure):
+    _fields_ = [
+        ("n_nodes", C.c_int32), ("n_words", C.c_int32), ("device", C.c_int32),
+        ("n_states", C.c_uint64), ("table_slots", C.c_uint64), ("max_probe", C.c_uint32),
+    ]
+
+
+STATESET_MAX_STATES = 1 << 24
+
 _PP = C.POINTER(_vp)
 
 # name -> (restype, argtypes); mirrors include/pbn_abi.h one to one
@@ -163,6 +172,13 @@ SIGNATURES = {
     "pbn_reach_mark_backward": (C.c_int, [_vp, _u64p, _u64p]),
     "pbn_reach_read": (C.c_int, [_vp, _u64p, _u32p, C.c_uint64, _u64p]),
     "pbn_reach_hull": (C.c_int, [_vp, _u64p, _u64p]),
+    "pbn_stateset_create": (C.c_int, [C.c_int32, C.c_int, _u64p, _i32p, C.c_uint64, _PP]),
+    "pbn_stateset_destroy": (None, [_vp]),
+    "pbn_stateset_get_info": (C.c_int, [_vp, C.POINTER(StateSetInfo)]),
+    "pbn_stateset_lookup": (C.c_int, [_vp, _u64p, C.c_uint64, _i32p]),
+    "pbn_stateset_lookup_device": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "pbn_tenv_step_device": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int, _vp, _vp, _vp, _vp]),
+    "pbn_tenv_reset_device": (C.c_int, [_vp, _vp, C.c_uint64, _vp]),
 }
 
 

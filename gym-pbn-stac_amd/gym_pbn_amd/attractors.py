@@ -253,6 +253,18 @@ class AttractorResult:
         the form ``PBNEnv`` / ``VecPBNEnv`` take as ``all_attractors``."""
         return [[tuple(int(v) for v in row) for row in unpack_bits(a, self.n_nodes)] for a in self.attractors]
 
+    def state_set(self, device: Optional[int] = 0):
+        """One labelled :class:`gym_pbn_amd.stateset.StateSet` of every found attractor, label = the attractor's
+        index: ``np.bincount(batch.classify_host(s) + 1)`` over a settled batch is the landing histogram
+        (bin 0: envs in no found attractor). ``device=None``: the host copy only."""
+        from .stateset import StateSet
+
+        W = (self.n_nodes + 63) // 64
+        rows = np.concatenate(self.attractors) if self.attractors else np.zeros((0, W), np.uint64)
+        labels = np.concatenate([np.full(len(a), j, np.int32) for j, a in enumerate(self.attractors)]) \
+            if self.attractors else np.zeros(0, np.int32)
+        return StateSet(rows, self.n_nodes, labels=labels, device=device)
+
 
 def _known(found, s) -> int:
     """Index of the found attractor holding state ``s``, or -1. Attractors are disjoint, so one state decides."""

@@ -401,6 +401,40 @@ class PBNBatch:
                                                    C.c_void_p(d_obs), C.c_void_p(d_reward), C.c_void_p(d_flags),
                                                    C.c_void_p(d_n_updates)))
 
+    # -- exact state sets (gym_pbn_amd.stateset) ------------------------------
+    def classify(self, stateset, d_labels_ptr: int, d_words_ptr: int = 0):
+        """Device lookup, one launch, asynchronous: int32 ``[B]`` labels at ``d_labels_ptr`` of the batch's
+        state (``d_words_ptr`` 0) or of device words ``[B][W]`` in ``stateset`` (-1: not a member)."""
+        L.check(L.lib.pbn_stateset_lookup_device(self._h, stateset.handle, C.c_void_p(d_words_ptr or None),
+                                                 C.c_void_p(d_labels_ptr)))
+
+    def classify_host(self, stateset) -> np.ndarray:
+        """:meth:`classify` of the batch's state into a numpy ``[B]`` int32 array (a convenience: the labels
+        live in a torch tensor on the way)."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        torch.cuda.synchronize(dev)  # the batch's stream does not order against torch's allocator
+        out = torch.empty(self.n_envs, dtype=torch.int32, device=dev)
+        self.classify(stateset, out.data_ptr())
+        self.sync()
+        return out.cpu().numpy()
+
+    def tenv_step_device(self, target, d_actions: int, d_reward: int, d_flags: int, d_obs: int = 0, d_labels: int = 0,
+                         reward_target: int = 20, step_cost: int = 4, action_cost: int = 1, check: bool = False):
+        """The ``PBN-v0`` step (``pbn_env.py:125-188``) of every env in one launch, on device buffers: flip node
+        ``a`` (``a != 0``), one ``PBN.step`` update (the draw ``step(1)`` would make), membership in the
+        :class:`~gym_pbn_amd.stateset.StateSet` ``target``, reward and flags. Asynchronous unless ``check``."""
+        L.check(L.lib.pbn_tenv_step_device(self._h, target.handle, C.c_void_p(d_actions), int(reward_target),
+                                           int(step_cost), int(action_cost), int(bool(check)),
+                                           C.c_void_p(d_obs or None), C.c_void_p(d_reward), C.c_void_p(d_flags),
+                                           C.c_void_p(d_labels or None)))
+
+    def tenv_reset_device(self, d_states: int, n_states: int, d_mask: int = 0):
+        """Envs with ``d_mask[e] != 0`` (0 = all) take a row of device ``d_states`` ``[n_states][W]`` drawn
+        uniformly (Philox stream 9), node 0 cleared; asynchronous."""
+        L.check(L.lib.pbn_tenv_reset_device(self._h, C.c_void_p(d_states), int(n_states), C.c_void_p(d_mask or None)))
+
     def synch_step(self, n_steps: int = 1, perturbation_prob: float = 0.0):
         """Synchronous update (base.py:286-303); perturbation_prob > 0 enables perturbations (p=0.001 there)."""
         gap = flip_gap_table(self.n_nodes, perturbation_prob)

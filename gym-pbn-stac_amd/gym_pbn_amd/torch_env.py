@@ -12,6 +12,10 @@ Same transition, reward, termination and truncation as :class:`gym_pbn_amd.envs.
 (one R6 launch per call; Philox draws keyed by the global env id); ``auto_reset`` resets the
 envs that ended, on the device, after their outputs were written (SB3 VecEnv convention; the
 reference env never resets itself).
+
+:class:`TorchVecPBNEnv` is the same for the ``PBN-v0`` MDP of truth-table networks (``pbn_env.py:125-188``): the
+device twin of :class:`gym_pbn_amd.envs.VecPBNEnv`, one fused launch per step over an exact device set of target
+states (:mod:`gym_pbn_amd.stateset`).
 """
 
 from __future__ import annotations
@@ -115,4 +119,191 @@ class TorchVecPBNTargetMultiEnv:
         self.batch.close()
 
 
-__all__ = ["TorchVecPBNTargetMultiEnv"]
+def _packed_attractors(network, net, all_attractors, device: int, seed: int):
+    """``all_attractors`` in any accepted form -> a list of packed ``[S_k][W]`` uint64 arrays (no tuples made
+    for the forms that are packed already)."""
+    import numpy as np
+
+    from .attractors import AttractorResult, find_attractors
+    from .batch import pack_bits
+
+    W = network.n_words
+    if all_attractors is None:  # the full STG, as PBNEnv / VecPBNEnv (pbn_env.py:54)
+        from .stg import compute_attractors
+
+        all_attractors = compute_attractors(network)
+    elif isinstance(all_attractors, str):
+        if all_attractors != "find":
+            raise ValueError(f"all_attractors={all_attractors!r}: a list, an AttractorResult, \"find\" or None")
+        res = find_attractors(net, device=device, seed=seed, table_graph="stg")
+        if not res.attractors:
+            raise RuntimeError(f"no attractor fits the state set: {len(res.incomplete)} closure(s) ran past max_states")
+        if res.incomplete:
+            import warnings
+
+            warnings.warn(f"{sum(e['n_seeds'] for e in res.incomplete)} seed(s) ended in closures past max_states; "
+                          "the env uses the attractors that were enumerated")
+        all_attractors = res
+    if isinstance(all_attractors, AttractorResult):
+        if all_attractors.n_nodes != network.n_nodes:
+            raise ValueError(f"attractors of {all_attractors.n_nodes} nodes for a network of {network.n_nodes}")
+        all_attractors = all_attractors.attractors
+    out = []
+    for a in all_attractors:
+        if isinstance(a, np.ndarray) and a.dtype == np.uint64:
+            out.append(np.ascontiguousarray(a).reshape(-1, W))
+        else:  # state tuples, node 0 first
+            bits = np.array([tuple(int(v) for v in s) for s in a], dtype=np.uint8).reshape(-1, network.n_nodes)
+            out.append(pack_bits(bits).reshape(-1, W))
+    if not out or not all(len(a) for a in out):
+        raise ValueError("need at least one non-empty attractor")
+    return out
+
+
+class TorchVecPBNEnv:
+    """B copies of the ``PBN-v0`` MDP (``pbn_env.py:125-188``) resident on the device: the twin of
+    :class:`gym_pbn_amd.envs.VecPBNEnv` for agents on the GPU.
+
+    ``step(actions)`` takes an int tensor ``[B]`` on the device (0 = no action, ``a`` flips node ``a``) and is one
+    launch (``pbn_tenv_step_device``): flip, one ``PBN.step`` update, membership of the new state in the target
+    set, reward and flags; it returns device tensors ``(obs [B][N] uint8, reward [B] int32, terminated [B] bool,
+    truncated [B] bool, info)`` with ``info["obs_words"]`` (packed ``[B][W]`` int64) and ``info["label"]`` (the
+    target set's label of each env's state, -1 outside). Nothing crosses PCIe per step, and the attractors may
+    hold up to ``2**24`` states (the host envs keep Python sets and stop at ``2**16``).
+
+    Same transitions, rewards (the reference's literals 20 / -4 / -1) and termination as ``VecPBNEnv`` for the
+    same seed. ``reset`` and ``auto_reset`` draw from the attracting states on the device
+    (``pbn_tenv_reset_device``: Philox stream 9, counter ``{0, reset_count, global env id}``, row =
+    ``mulhi(word 0, n)``), so their picks differ from ``VecPBNEnv``'s host ``default_rng`` draws: a documented
+    stream of its own.
+
+    ``all_attractors``: ``None`` (the full STG, up to 22 nodes); a list of attractors, each a list of state
+    tuples or a packed ``[S][W]`` uint64 array; an :class:`~gym_pbn_amd.attractors.AttractorResult`; or
+    ``"find"`` (:func:`~gym_pbn_amd.attractors.find_attractors` on the ``"stg"`` graph, no limit on their
+    size but the set's). The target set is ``goal_config["target_nodes"]`` united with every attractor that
+    meets it (``pbn_env.py:57-59``).
+    """
+
+    REWARD_TARGET, STEP_COST, ACTION_COST = 20, 4, 1  # pbn_env.py:156-188
+
+    def __init__(self, PBN_data=None, logic_func_data=None, goal_config=None, n_envs: int = 1, *,
+                 all_attractors=None, device: int = 0, seed: int = 0, env_id_base: int = 0, auto_reset: bool = False):
+        import numpy as np
+        import torch
+
+        from .attractors import rows_in
+        from .batch import pack_bits
+        from .network import TruthTableNetwork
+        from .stateset import StateSet
+
+        if PBN_data is not None and len(PBN_data) != 0:
+            net = TruthTableNetwork.from_pbn_data(PBN_data)
+        elif logic_func_data is not None:
+            net = TruthTableNetwork.from_logic_funcs(*logic_func_data)
+        else:
+            raise ValueError("TorchVecPBNEnv needs PBN_data or logic_func_data")
+        if goal_config is None or "target_nodes" not in goal_config:
+            raise KeyError("target_nodes")  # pbn_env.py:51
+        self.network = net
+        self.net = Net(net)
+        self.N, self.W = net.n_nodes, net.n_words
+        self.num_envs = int(n_envs)
+        self.device = torch.device("cuda", device)
+        self.attractors = _packed_attractors(net, self.net, all_attractors, device, seed)
+        # target expansion on packed rows (pbn_env.py:57-59): the union of the target and every attractor meeting it
+        tn = [tuple(int(v) for v in s) for s in goal_config["target_nodes"]]
+        base = pack_bits(np.array(tn, dtype=np.uint8).reshape(-1, self.N)).reshape(-1, self.W)
+        parts = [base] + [a for a in self.attractors if rows_in(a, base).any()]
+        target = np.unique(np.concatenate(parts), axis=0)
+        self.target_words = target
+        self.target = StateSet(target, self.N, device=device)
+        attracting = np.unique(np.concatenate(self.attractors), axis=0)
+        self.n_attracting = int(attracting.shape[0])
+        self.batch = PBNBatch(self.net, self.num_envs, device=device, env_id_base=env_id_base, seed=seed)
+        self.auto_reset = bool(auto_reset)
+        self.observation_space = spaces.bool_multibinary(self.N)  # pbn_env.py:81-83
+        self.action_space = spaces.Discrete(self.N)
+        B = self.num_envs
+        with torch.cuda.device(self.device):
+            # uploaded once: the table reset and auto-reset draw from
+            self._attracting = torch.from_numpy(attracting.view(np.int64)).to(self.device).contiguous()
+            self._flags = torch.empty(B, dtype=torch.uint8, device=self.device)
+        self._use_stream()
+
+    def _use_stream(self):
+        import torch
+
+        self.batch.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def info(self) -> dict:
+        """The target set's ``pbn_stateset_info`` (``n_states``, ``table_slots``, ``max_probe``, ...) and
+        ``n_attracting``, the number of attracting states reset draws from."""
+        d = self.target.info()
+        d["n_attracting"] = self.n_attracting
+        return d
+
+    def _bits(self, words=None):
+        import torch
+
+        out = torch.empty((self.num_envs, self.N), dtype=torch.uint8, device=self.device)
+        self.batch.unpack_bits_device(out.data_ptr(), 0 if words is None else words.data_ptr())
+        return out
+
+    def observation_words(self):
+        import torch
+
+        self._use_stream()
+        words = torch.empty((self.num_envs, self.W), dtype=torch.int64, device=self.device)
+        self.batch.get_state_device(words.data_ptr())
+        return words
+
+    def reset(self, mask=None):
+        """Every env (``mask`` None) or the envs where the device bool / uint8 ``mask`` is set take a state drawn
+        uniformly from the attracting set, node 0 cleared (``PBN.reset``, ``pbn.py:118``); returns observations
+        ``[B][N]`` uint8 on the device."""
+        import torch
+
+        self._use_stream()
+        if mask is None:
+            self.batch.tenv_reset_device(self._attracting.data_ptr(), self.n_attracting, 0)
+        else:
+            m = mask.to(device=self.device, dtype=torch.uint8).contiguous()
+            self.batch.tenv_reset_device(self._attracting.data_ptr(), self.n_attracting, m.data_ptr())
+        return self._bits()
+
+    def step(self, actions, check: bool = False):
+        """``actions``: int tensor ``[B]`` on the GPU, values in ``[0, N-1]``. An env given any other value is left
+        untouched, outputs included; ``check=True`` waits for the launch and raises ``ValueError`` then (the
+        default stays asynchronous, and a later checked call reports)."""
+        import torch
+
+        a = actions.to(device=self.device, dtype=torch.int32).contiguous().reshape(-1)
+        if a.shape[0] != self.num_envs:
+            raise ValueError(f"actions for {a.shape[0]} envs, the batch has {self.num_envs}")
+        self._use_stream()
+        B = self.num_envs
+        words = torch.empty((B, self.W), dtype=torch.int64, device=self.device)
+        reward = torch.empty(B, dtype=torch.int32, device=self.device)
+        label = torch.empty(B, dtype=torch.int32, device=self.device)
+        self.batch.tenv_step_device(self.target, a.data_ptr(), reward.data_ptr(), self._flags.data_ptr(),
+                                    d_obs=words.data_ptr(), d_labels=label.data_ptr(),
+                                    reward_target=self.REWARD_TARGET, step_cost=self.STEP_COST,
+                                    action_cost=self.ACTION_COST, check=check)
+        term = (self._flags & L.FLAG_TERMINATED) != 0
+        trunc = torch.zeros(B, dtype=torch.bool, device=self.device)
+        obs = self._bits(words)
+        if self.auto_reset:
+            done = term.to(torch.uint8).contiguous()
+            self.batch.tenv_reset_device(self._attracting.data_ptr(), self.n_attracting, done.data_ptr())
+        return obs, reward, term, trunc, {"obs_words": words, "label": label}
+
+    def close(self):
+        import torch
+
+        torch.cuda.current_stream(self.device).synchronize()
+        self.batch.set_stream(None)
+        self.batch.close()
+        self.target.close()
+
+
+__all__ = ["TorchVecPBNTargetMultiEnv", "TorchVecPBNEnv"]

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define PBN_ABI_VERSION 18
+#define PBN_ABI_VERSION 19
 
 enum {
     PBN_OK = 0,
@@ -375,6 +375,55 @@ int pbn_reach_read(pbn_reach *r, uint64_t *states, uint32_t *marks, uint64_t cap
 /* Hull cube of the set (base.py:398-399's components as one cabean-style cube): all_words / any_words [W] = AND / OR
  * over all states; node i is fixed in the hull iff bit i of all ^ any is 0. Valid for an incomplete closure too. */
 int pbn_reach_hull(pbn_reach *r, uint64_t *all_words, uint64_t *any_words);
+
+/* ---- exact state sets: `state in attractor` / `state in target_nodes` (pbn_env.py:57-59, 161) for a whole batch ----
+ * The reference envs keep their attractors and targets as Python sets of state tuples. A pbn_stateset is the same
+ * thing for packed states: an exact, read-only, labelled set that a kernel can query (csrc/pbn_stateset.hpp has
+ * the one definition of its layout and walk, for host and kernels). Open addressing, linear probing, table_slots =
+ * the power of two >= 2 * n_states (at least 64); label = the caller's int per state (e.g. the attractor's index).
+ * Bits past node N-1 must be zero in members (PBN_E_INVALID) and in queries (such a query is no member). */
+#define PBN_STATESET_MAX_STATES ((uint64_t)1 << 24)
+typedef struct pbn_stateset pbn_stateset;
+typedef struct {
+    int32_t n_nodes, n_words, device; /* device -1: host copy only */
+    uint64_t n_states;                /* distinct members */
+    uint64_t table_slots;
+    uint32_t max_probe;               /* the longest walk of any member (1 = at its home slot; 0: the empty set) */
+} pbn_stateset_info;
+/* states [S][W] host, labels [S] (NULL = all 0), S <= PBN_STATESET_MAX_STATES. Built on the host, sequentially, in
+ * input order (a deterministic layout). A duplicate row with the same label is dropped; with another label, or a
+ * label < 0: PBN_E_INVALID. device >= 0: host copy + upload; device == -1: host copy only (the pbn_net_unstable
+ * precedent: pins the definition on a machine without a GPU; device calls then return PBN_E_STATE). */
+int pbn_stateset_create(int32_t n_nodes, int device, const uint64_t *states, const int32_t *labels, uint64_t n_states,
+                        pbn_stateset **out);
+void pbn_stateset_destroy(pbn_stateset *s);
+int pbn_stateset_get_info(const pbn_stateset *s, pbn_stateset_info *info);
+/* Host lookup over the host copy: labels [n] = the label of states [n][W], -1 for a non-member. */
+int pbn_stateset_lookup(const pbn_stateset *s, const uint64_t *states, uint64_t n, int32_t *labels);
+/* Device lookup, one launch: d_labels [B] int32 (device) = labels of the batch's state (d_words NULL) or of device
+ * words [B][W] (16-byte aligned). Asynchronous, on the batch's stream. Set and batch on different devices or with
+ * different n_nodes: PBN_E_INVALID; a host-only set: PBN_E_STATE. */
+int pbn_stateset_lookup_device(pbn_batch *b, const pbn_stateset *s, const void *d_words, int32_t *d_labels);
+
+/* ---- PBN-v0 on the device: PBNEnv.step / _get_reward (pbn_env.py:125-188) for every env in one launch ----
+ * PROB_TABLE batches only (PREDICTOR_MIX: PBN_E_UNSUPPORTED). Device arrays, asynchronous, on the batch's stream.
+ * d_actions [B] int32: 0 = none, a in [1, N-1] flips node a (PBNEnv flips `action`, :141-142); then one PBN.step
+ * update with exactly the draw pbn_step would make (the batch's update counter advances by 1, so pbn_flip +
+ * pbn_step(1) and this call give the same state bit for bit, and the calls mix freely); then per env
+ * terminated = state in target, reward = terminated ? reward_target : -(step_cost + (a != 0 ? action_cost : 0))
+ * (the reference's literals: 20, 4, 1), flags = PBN_FLAG_TERMINATED or 0 (PBN-v0 never truncates).
+ * d_obs [B][W] (the state after the step) and d_labels [B] (the target set's label, -1 outside) may be NULL.
+ * An env whose action is outside [0, N-1] is skipped whole -- no flip, no update, its outputs left as they were --
+ * and noted in a sticky device flag (the pbn_flip_device convention): check 1 waits, returns PBN_E_RANGE if the flag
+ * is set and clears it; check 0 returns at once. The update counter advances either way. */
+int pbn_tenv_step_device(pbn_batch *b, const pbn_stateset *target, const int32_t *d_actions, int32_t reward_target,
+                         int32_t step_cost, int32_t action_cost, int check, uint64_t *d_obs, int32_t *d_reward,
+                         uint8_t *d_flags, int32_t *d_labels);
+/* Envs with d_mask[e] != 0 (NULL = all) take a state drawn uniformly from d_states [n_states][W] (device, 16-byte
+ * aligned; e.g. the attracting states), node 0 cleared as PBN.reset does (pbn.py:118). Draw: Philox stream 9,
+ * counter {0, reset_count, global env id}, row = mulhi(word 0, n_states); reset_count advances by 1 per call
+ * (modulo 2^32). n_states == 0 or >= 2^32: PBN_E_INVALID. */
+int pbn_tenv_reset_device(pbn_batch *b, const uint64_t *d_states, uint64_t n_states, const uint8_t *d_mask);
 
 #ifdef __cplusplus
 }
