@@ -21,6 +21,9 @@ What is captured (SURVEY §8c "Golden vectors to commit"):
   de-duplicated as at ``:120-121``; plus list rows, not de-duplicated). The
   attractor hypercubes are synthetic (cabean is unavailable) and expanded into
   ``attracting_states`` exactly as ``:437-455`` does.
+* ``r1_syn<N>.npz`` / ``r4_ttk3_<N>.npz`` (``make_golden.py shapes``) -- the same two captures on the
+  synthetic networks of ``tests/shape_cases.py`` at the state widths and ``N % 64 == 0`` edges the bundled
+  networks do not reach; the reference ``Graph`` is built from ``synthetic_predictor_sets`` itself.
 * ``r1_mt_<net>.npz`` -- long R1 runs keyed only by the Python seed, for the
   device MT19937 mode (``random.seed(s)`` + ``genRandState`` + T steps; final
   states and a digest of every intermediate state).
@@ -41,13 +44,14 @@ HERE = Path(__file__).resolve().parent
 REPO = HERE.parents[1]
 sys.path.insert(0, str(HERE))
 sys.path.insert(0, str(REPO / "gym-pbn-stac_amd"))
+sys.path.insert(0, str(REPO / "tests"))
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import refload  # noqa: E402
 from gym_pbn_amd.io.safe_pickle import load_pickle_safely  # noqa: E402
-from gym_pbn_amd.network import load_network, synthetic_truth_table_pbn  # noqa: E402
+from gym_pbn_amd.network import load_network, synthetic_predictor_sets, synthetic_truth_table_pbn  # noqa: E402
 
 BITTNER = Path("/root/reference/gym_PBN/envs/bittner/data")
 PICKLES = {"bittner28": "predictor_sets_28_15_median.pkl", "bittner199": "predictor_sets_200_5_kmeans.pkl",
@@ -79,10 +83,15 @@ def pairs(log, first="i", second="u"):
     return out
 
 
-def gen_r1(base, name, seeds=(0, 1, 2, 3), T=2000):
-    net = load_network(name)
-    ps = load_pickle_safely(BITTNER / PICKLES[name])
-    g = refload.build_graph(base, ps, net.node_ids)
+def gen_r1(base, name, seeds=(0, 1, 2, 3), T=2000, synthetic=None):
+    """``synthetic=(n, max_preds, data_seed)``: the reference Graph of ``synthetic_predictor_sets`` (the
+    structure of the reference's pickles) instead of a Bittner pickle."""
+    if synthetic is None:
+        net = load_network(name)
+        ps, node_ids = load_pickle_safely(BITTNER / PICKLES[name]), net.node_ids
+    else:
+        ps, node_ids = synthetic_predictor_sets(*synthetic)
+    g = refload.build_graph(base, ps, node_ids)
     rec = refload.DrawRecorder(random)
     base.random = rec
     out = {"seeds": np.array(seeds, dtype=np.int64)}
@@ -526,6 +535,13 @@ def main():
     if not only or "r4" in only:
         gen_r4(pbn_mod, node_mod, "tt200", 200, 4, 0)
         gen_r4(pbn_mod, node_mod, "tt8", 8, 3, 1, T=3000)
+    if "shapes" in only:  # not part of the default run: the widths and N % 64 == 0 edges of shape_cases.py
+        import shape_cases as sc
+
+        for n in sc.GOLDEN_R1:
+            gen_r1(base, f"syn{n}", seeds=(0, 1), T=300, synthetic=(n, sc.PM_MAX_PREDS, n))
+        for n in sc.GOLDEN_R4:
+            gen_r4(pbn_mod, node_mod, f"ttk3_{n}", n, sc.TT_K, n, seeds=(0, 1), T=300)
     if not only or "mt" in only:
         gen_r1_mt(base, "bittner28")
         gen_r1_mt(base, "bittner199", T=3000)

@@ -49,9 +49,11 @@ def test_unstable_bundled_nets(name, count):
     assert np.array_equal(got, np_unstable_words(net, states))
 
 
-@pytest.mark.parametrize("n_total", [64, 65])
+@pytest.mark.parametrize("n_total", [64, 65, 128, 192, 256, 257, 384, 448, 512])  # every W = 1 .. 8
 def test_unstable_embedded_across_the_word_boundary(n_total):
-    """A golden N = 10 net inside 64 / 65 nodes, its nodes ending at bit 63 / straddling bits 63 and 64."""
+    """A golden N = 10 net inside 64 / 65 / ... nodes, at the top of the range: its nodes ending at bit 63 /
+    straddling bits 63 and 64, and the same in the last word of every state width up to W = 8 (N = 512: ending
+    at the last bit there is)."""
     from gym_pbn_amd.attractors import ReachSet
 
     c = case_by(10, 2, 0)

@@ -48,10 +48,11 @@ def test_unstable_tt200(graph):
 
 
 @pytest.mark.parametrize("graph", GRAPHS)
-@pytest.mark.parametrize("n_total", [64, 65])
+@pytest.mark.parametrize("n_total", [64, 65, 128, 192, 256, 257, 384, 448, 512])  # every W = 1 .. 8
 def test_unstable_embedded_across_the_word_boundary(n_total, graph):
     """The edge-value network (k = 0 .. 6 side by side in one wave, tables holding the doubles next to 0 and 1)
-    inside 64 / 65 nodes, its nodes ending at bit 63 / straddling bits 63 and 64."""
+    inside 64 / 65 / ... nodes, at the top of the range: its nodes ending at bit 63 / straddling bits 63 and 64,
+    and the same in the last word of every state width up to W = 8 (N = 512: ending at the last bit there is)."""
     from gym_pbn_amd.attractors import ReachSet
 
     small = edge_value_network()

@@ -13,6 +13,7 @@ import pytest
 from conftest import cubes_to_attractors, golden, r6_config
 from gym_pbn_amd.network import load_network
 from r6_cases import ENV_VARIANT_CASES, env_variant_setup
+from shape_cases import GOLDEN_R1, GOLDEN_R4, pm_net, tt_net
 
 pytestmark = pytest.mark.gpu
 
@@ -27,12 +28,16 @@ def G():
 
 # ----------------------------------------------------------------- replay vs reference fixtures
 @pytest.mark.parametrize("name,kind", [("bittner28", "r1"), ("bittner199", "r1"), ("bittner70", "r1"),
-                                       ("tt200", "r4"), ("tt8", "r4")])
+                                       ("tt200", "r4"), ("tt8", "r4")]
+                         + [(f"syn{n}", "r1") for n in GOLDEN_R1] + [(f"ttk3_{n}", "r4") for n in GOLDEN_R4])
 def test_replay_matches_reference_trajectories(G, name, kind):
-    """Feed the reference's own draws; every intermediate state must equal the reference's."""
+    """Feed the reference's own draws; every intermediate state must equal the reference's. ``syn<N>`` /
+    ``ttk3_<N>`` are the shape table's networks (every state width, ``N % 64 == 0``), built in memory."""
     z = golden(f"{kind}_{name}.npz")
     S, T = z["node_idx"].shape
-    b = G.PBNBatch(name, S)
+    net = pm_net(int(name[3:])) if name.startswith("syn") else tt_net(int(name[5:])) if name.startswith("ttk3_") \
+        else name
+    b = G.PBNBatch(net, S)
     b.set_state(z["init"])
     # one update per call for the first 64 steps (state round-trips HBM), then the rest in one launch
     for t in range(64):

@@ -14,6 +14,17 @@ import pytest
 
 from conftest import golden, r6_config
 from gym_pbn_amd.network import load_network
+from shape_cases import GOLDEN_R1, GOLDEN_R4, pm_net, tt_net
+
+
+def _net(name):
+    """A bundled network, or the shape table's synthetic one (``syn<N>`` / ``ttk3_<N>``: the widths and
+    ``N % 64 == 0`` edges of ``shape_cases.py``, built in memory like their goldens were)."""
+    if name.startswith("syn"):
+        return pm_net(int(name[3:]))
+    if name.startswith("ttk3_"):
+        return tt_net(int(name[5:]))
+    return load_network(name)
 
 
 @pytest.mark.parametrize("seed", [0, 1, 42, 12345, 2**32 + 7, 2**63 + 11])
@@ -43,10 +54,10 @@ def test_philox_kat(oracle_mod):
         [0xD16CFE09, 0x94FDCCEB, 0x5001E420, 0x24126EA1]
 
 
-@pytest.mark.parametrize("name", ["bittner28", "bittner199", "bittner70"])
+@pytest.mark.parametrize("name", ["bittner28", "bittner199", "bittner70"] + [f"syn{n}" for n in GOLDEN_R1])
 def test_r1_replay_matches_reference(oracle_mod, name):
     z = golden(f"r1_{name}.npz")
-    o = oracle_mod.Oracle(load_network(name))
+    o = oracle_mod.Oracle(_net(name))
     for si in range(len(z["seeds"])):
         st = z["init"][si][None]
         for t in range(z["states"].shape[1]):
@@ -54,10 +65,10 @@ def test_r1_replay_matches_reference(oracle_mod, name):
             assert np.array_equal(st[0], z["states"][si][t]), (si, t)
 
 
-@pytest.mark.parametrize("name", ["tt200", "tt8"])
+@pytest.mark.parametrize("name", ["tt200", "tt8"] + [f"ttk3_{n}" for n in GOLDEN_R4])
 def test_r4_replay_matches_reference(oracle_mod, name):
     z = golden(f"r4_{name}.npz")
-    o = oracle_mod.Oracle(load_network(name))
+    o = oracle_mod.Oracle(_net(name))
     for si in range(len(z["seeds"])):
         st = z["init"][si][None]
         for t in range(z["states"].shape[1]):

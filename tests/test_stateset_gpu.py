@@ -3,7 +3,8 @@
 Shapes: B = 257 (a second workgroup with one live lane) and B = 1; W = 1 (``tt8``) and W = 4 (``tt200``, nodes
 across word boundaries). ``tt8`` has 2^8 states, of which only 4 share home slot 63 of a 64-slot table, so the
 12-state wrapped walk cannot be built over it: there the colliding set is those 4 (walks that wrap, 4 long) and the
-full 12-state set runs on a 40-node synthetic network, still W = 1.
+full 12-state set runs on a 40-node synthetic network, still W = 1. Every other width (W = 1 .. 8, ``N % 64 == 0``,
+decoys in the last word) is in ``test_shape_sweep_gpu.py::test_stateset_classify``.
 """
 
 import numpy as np
