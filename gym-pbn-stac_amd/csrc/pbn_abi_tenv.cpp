@@ -1,6 +1,11 @@
-// pbn_abi_tenv.cpp -- exact state sets (pbn_stateset_*) and the PBN-v0 env on the device (pbn_tenv_*): the
-// entry points over pbn_stateset.hpp (the set's one definition) and the kernels of pbn_tenv.hip.
+// pbn_abi_tenv.cpp -- exact state sets (pbn_stateset_*), the PBN-v0 env and the macro-action envs on the device
+// (pbn_tenv_*): the entry points over pbn_stateset.hpp (the set's one definition) and the kernels of pbn_tenv.hip
+// and pbn_tenv_macro.hip.
 #include "pbn_host.hpp"
+
+static_assert((int)PBN_MACRO_INTERVAL == (int)TENV_MACRO_INTERVAL && (int)PBN_MACRO_TRIGGER == (int)TENV_MACRO_TRIGGER &&
+                  PBN_TENV_MACRO_MAX_T == TENV_MACRO_MAX_T,
+              "pbn_abi.h and pbn_params.hpp name the same modes and cap");
 
 // The set can serve this batch's launches: uploaded, on the batch's device, over states of the batch's width.
 static int check_set_for_batch(const pbn_batch* b, const pbn_stateset* s, const char* what) {
@@ -16,6 +21,26 @@ static int check_table_batch(const pbn_batch* b, const char* fn) {
     if (b->net->kind != PBN_KIND_PROB_TABLE)
         return fail(PBN_E_UNSUPPORTED, "%s steps the PBN-v0 env of a truth-table network; this batch holds a "
                                        "predictor-mix network (its env is pbn_env_step_multi)", fn);
+    return 0;
+}
+
+// The sticky range flag of the env kernels (k_tenv_step, k_tenv_macro): zeroed at allocation and after every check.
+static int tenv_error_flag(pbn_batch* b, int32_t** flag) {
+    if (!b->tenv.err.p) {
+        if (int rc = b->tenv.err.ensure(4)) return rc;
+        HIP_TRY(hipMemsetAsync(b->tenv.err.p, 0, 4, b->stream));
+    }
+    *flag = (int32_t*)b->tenv.err.p;
+    return 0;
+}
+
+// Waits for the batch's stream, reads the flag and clears it.
+static int tenv_read_error_flag(pbn_batch* b, int32_t* flag, int32_t* err) {
+    if (!b->pin.ready()) return fail(PBN_E_NOMEM, "pinned staging buffer");
+    HIP_TRY(hipMemcpyAsync(b->pin.p, flag, 4, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipMemsetAsync(flag, 0, 4, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    memcpy(err, b->pin.p, 4);
     return 0;
 }
 
@@ -120,12 +145,8 @@ int pbn_tenv_step_device(pbn_batch* b, const pbn_stateset* target, const int32_t
     if (int rc = check_set_for_batch(b, target, "the target set")) return rc;
     if (b->N < 2) return fail(PBN_E_UNSUPPORTED, "PBN.step updates a node in [1, N-1]: the network needs two nodes");
     SET_DEV(b);
-    int32_t* flag = (int32_t*)b->tenv.err.p;  // zeroed at allocation and after every check
-    if (!flag) {
-        if (int rc = b->tenv.err.ensure(4)) return rc;
-        flag = (int32_t*)b->tenv.err.p;
-        HIP_TRY(hipMemsetAsync(flag, 0, 4, b->stream));
-    }
+    int32_t* flag;
+    if (int rc = tenv_error_flag(b, &flag)) return rc;
     if (!b->tenv.bpc)
         if (int e = max_blocks_tenv(b->W, b->net->L.plane_off, &b->tenv.bpc))
             return fail(PBN_E_HIP, "occupancy query: %s", hipGetErrorString((hipError_t)e));
@@ -151,13 +172,82 @@ int pbn_tenv_step_device(pbn_batch* b, const pbn_stateset* target, const int32_t
     if (int rc = timed_launch(b, "k_tenv_step", [&] { return launch_tenv_step(b->W, a, grid, b->stream); })) return rc;
     b->update_count++;  // the launch happened: the count advances whether or not an action was refused
     if (!check) return 0;
-    if (!b->pin.ready()) return fail(PBN_E_NOMEM, "pinned staging buffer");
-    HIP_TRY(hipMemcpyAsync(b->pin.p, flag, 4, hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipMemsetAsync(flag, 0, 4, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
     int32_t err;
-    memcpy(&err, b->pin.p, 4);
+    if (int rc = tenv_read_error_flag(b, flag, &err)) return rc;
     if (err) return fail(PBN_E_RANGE, "Invalid action: a value outside [0, %d] (envs holding one were left untouched)", b->N - 1);
+    return 0;
+}
+
+int pbn_tenv_macro_device(pbn_batch* b, const pbn_stateset* target, int mode, uint32_t t_max, const int32_t* d_actions,
+                          const int32_t* d_limit, const double* d_gpow, const uint64_t* d_stop_thr,
+                          int32_t reward_target, int32_t step_cost, int32_t action_cost, int check, uint64_t* d_obs,
+                          int32_t* d_reward_i32, double* d_reward_f64, uint8_t* d_flags, int32_t* d_interval,
+                          int32_t* d_first_hit, int32_t* d_labels) {
+    CHECK_NN(b, "batch");
+    CHECK_NN(target, "target");
+    CHECK_NN(d_actions, "d_actions");
+    CHECK_NN(d_limit, "d_limit");
+    CHECK_NN(d_flags, "d_flags");
+    if (mode != PBN_MACRO_INTERVAL && mode != PBN_MACRO_TRIGGER)
+        return fail(PBN_E_INVALID, "mode=%d: PBN_MACRO_INTERVAL (%d) or PBN_MACRO_TRIGGER (%d)", mode,
+                    (int)PBN_MACRO_INTERVAL, (int)PBN_MACRO_TRIGGER);
+    if (mode == PBN_MACRO_INTERVAL) {
+        CHECK_NN(d_reward_i32, "d_reward_i32");
+    } else {
+        CHECK_NN(d_reward_f64, "d_reward_f64");
+        CHECK_NN(d_gpow, "d_gpow");
+        CHECK_NN(d_stop_thr, "d_stop_thr");
+    }
+    if (t_max < 1 || t_max > PBN_TENV_MACRO_MAX_T)
+        return fail(PBN_E_INVALID, "t_max=%u outside [1, PBN_TENV_MACRO_MAX_T = %u]", (unsigned)t_max,
+                    (unsigned)PBN_TENV_MACRO_MAX_T);
+    if (int rc = check_table_batch(b, "pbn_tenv_macro_device")) return rc;
+    if (int rc = check_set_for_batch(b, target, "the target set")) return rc;
+    if (b->N < 2) return fail(PBN_E_UNSUPPORTED, "PBN.step updates a node in [1, N-1]: the network needs two nodes");
+    SET_DEV(b);
+    int32_t* flag;
+    if (int rc = tenv_error_flag(b, &flag)) return rc;
+    int& bpc = b->tenv.macro_bpc[mode];
+    if (!bpc)
+        if (int e = max_blocks_tenv_macro(b->W, mode, b->net->L.plane_off, &bpc))
+            return fail(PBN_E_HIP, "occupancy query: %s", hipGetErrorString((hipError_t)e));
+    TenvMacroArgs a{};
+    a.state = b->d_state;
+    a.img = b->d_image;
+    a.L = b->net->L;
+    a.B = b->B;
+    a.env_base = b->env_base;
+    a.seed = b->seed;
+    a.update = b->update_count;
+    a.actions = d_actions;
+    a.limit = d_limit;
+    a.target = target->view();
+    a.reward_target = reward_target;
+    a.step_cost = step_cost;
+    a.action_cost = action_cost;
+    a.mode = mode;
+    a.t_max = t_max;
+    a.gpow = d_gpow;
+    a.stop_thr = d_stop_thr;
+    a.obs = d_obs;
+    a.reward_i32 = d_reward_i32;
+    a.reward_f64 = d_reward_f64;
+    a.flags = d_flags;
+    a.interval = d_interval;
+    a.first_hit = d_first_hit;
+    a.labels = d_labels;
+    a.error = flag;
+    const int grid = b->grid_for(b->B, bpc);
+    if (int rc = timed_launch(b, "k_tenv_macro", [&] { return launch_tenv_macro(b->W, a, grid, b->stream); })) return rc;
+    // t_max, not the longest run of rounds (which the host does not know): the next call's draws stay disjoint from
+    // this one's whatever the envs did, and whether or not an env was refused
+    b->update_count += t_max;
+    if (!check) return 0;
+    int32_t err;
+    if (int rc = tenv_read_error_flag(b, flag, &err)) return rc;
+    if (err)
+        return fail(PBN_E_RANGE, "Invalid action: an action outside [0, %d] or a limit outside [1, %u] (envs holding "
+                                 "one were left untouched)", b->N, mode == PBN_MACRO_INTERVAL ? (unsigned)t_max : 10u);
     return 0;
 }
 

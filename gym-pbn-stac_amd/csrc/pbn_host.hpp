@@ -259,6 +259,7 @@ struct pbn_batch {
     struct Tenv {        // the PBN-v0 env on the device (pbn_abi_tenv.cpp)
         DevBuf err;      // sticky range flag of pbn_tenv_step_device, zeroed at allocation and after every check
         int bpc = 0;     // k_tenv_step's resident workgroups per CU (0: not asked yet)
+        int macro_bpc[2] = {0, 0};  // k_tenv_macro's, by mode
     } tenv;
     // timing: mode 1 = an event pair around every launch; mode 2 = one region
     // (start before the first launch after enabling, stop after the latest launch)

@@ -14,7 +14,10 @@ enum {
     STREAM_SSD_FLIP = 6,
     STREAM_SYNC = 7,
     STREAM_SYNC_PERT = 8,
-    STREAM_TENV_RESET = 9  // pbn_tenv_reset_device: ctr {0, reset_count, env id}, row = mulhi(w[0], n_states)
+    STREAM_TENV_RESET = 9,  // pbn_tenv_reset_device: ctr {0, reset_count, env id}, row = mulhi(w[0], n_states)
+    // pbn_tenv_macro_device, trigger mode: the stop draw after update u of env g is ctr {u_lo, u_hi, g} (one call per
+    // env, not shared by an env pair), k53 = k53_of(w[0], w[1])
+    STREAM_TENV_TRIGGER = 10
 };
 // STORE_DIRTY / STORE_HALF write back the envs whose updated bit changed: the whole env, or (W even and >= 4,
 // 1024-thread step kernels) only the 16-B half that holds the bit (store_changed, pbn_device.hpp)
@@ -377,6 +380,36 @@ struct TenvArgs {
     int32_t* error;          // sticky: set to 1 by an env whose action names no node (the env is skipped)
 };
 
+// The macro-action envs (k_tenv_macro): up to t_max rounds of flip + update + lookup + reward per env in
+// one launch. TenvMacroArgs::mode and the kernel's template parameter (PBN_MACRO_* in pbn_abi.h).
+enum { TENV_MACRO_INTERVAL = 0, TENV_MACRO_TRIGGER = 1 };
+constexpr uint32_t TENV_MACRO_MAX_T = 65536;  // PBN_TENV_MACRO_MAX_T
+constexpr int32_t TENV_MACRO_MAX_PROB = 10;   // trigger mode: the stop probability in tenths
+
+struct TenvMacroArgs {
+    uint64_t* state;         // [B][W]
+    const void* img;         // truth-table network image
+    NetLayout L;
+    uint64_t B, env_base, seed;
+    uint64_t update;         // the batch's update counter: inner iteration i is update `update + i` of every env
+    const int32_t* actions;  // [B]: 0 = none, a in [1, N] flips node a - 1 before every inner update
+    const int32_t* limit;    // [B]: the interval in [1, t_max], or the stop probability in tenths in [1, 10]
+    SetView target;
+    int32_t reward_target, step_cost, action_cost;
+    int32_t mode;
+    uint32_t t_max;
+    const double* gpow;        // [t_max] gamma ** i (trigger mode)
+    const uint64_t* stop_thr;  // [11] floor((p / 10) 2^53), entry 0 unused (trigger mode)
+    uint64_t* obs;             // [B][W] or null: the final state
+    int32_t* reward_i32;       // [B] (interval mode)
+    double* reward_f64;        // [B] (trigger mode)
+    uint8_t* flags;            // [B]
+    int32_t* interval;         // [B] or null: inner iterations run
+    int32_t* first_hit;        // [B] or null: the first iteration whose state was in the target, or -1
+    int32_t* labels;           // [B] or null: the target set's label of the final state
+    int32_t* error;            // the sticky flag of TenvArgs::error
+};
+
 struct TenvResetArgs {
     uint64_t* state;
     uint64_t B, env_base, seed;
@@ -386,13 +419,16 @@ struct TenvResetArgs {
     const uint8_t* mask;     // [B] or null
 };
 
-// Launchers (pbn_step.hip, pbn_state.hip, pbn_env.hip, pbn_group.hip, pbn_mt.hip, pbn_ssd.hip, pbn_sync.hip, pbn_reach.hip). Return hipError_t as int.
+// Launchers (pbn_step.hip, pbn_state.hip, pbn_env.hip, pbn_group.hip, pbn_mt.hip, pbn_ssd.hip, pbn_sync.hip, pbn_reach.hip,
+// pbn_tenv.hip, pbn_tenv_macro.hip). Return hipError_t as int.
 enum { REACH_K_UNSTABLE = 0, REACH_K_SEED, REACH_K_EXPAND, REACH_K_BACK_START, REACH_K_BACK, REACH_K_HULL };
 int launch_reach(int W, int which, const ReachArgs& a, int grid, void* stream);
 int launch_set_lookup(int W, const SetLookupArgs& a, void* stream);
 int launch_tenv_step(int W, const TenvArgs& a, int grid, void* stream);
 int launch_tenv_reset(int W, const TenvResetArgs& a, void* stream);
 int max_blocks_tenv(int W, uint32_t image_bytes, int* blocks_per_cu);
+int launch_tenv_macro(int W, const TenvMacroArgs& a, int grid, void* stream);
+int max_blocks_tenv_macro(int W, int mode, uint32_t image_bytes, int* blocks_per_cu);
 int launch_bump(uint64_t* p, uint64_t k, void* stream);
 int launch_set_counters(uint64_t* p, uint64_t v, uint32_t n, void* stream);
 int launch_step(int W, const StepArgs& a, int store_mode, int replay, int sb, int grid, void* stream);

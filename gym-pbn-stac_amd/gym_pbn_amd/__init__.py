@@ -43,6 +43,11 @@ def __getattr__(name):
         from . import torch_env
 
         return getattr(torch_env, name)
+    if name in ("TorchVecPBNSampledDataEnv", "TorchVecPBNSelfTriggeringEnv", "stop_thresholds", "gamma_powers",
+                "decode_discrete"):
+        from . import macro_env
+
+        return getattr(macro_env, name)
     if name == "make":
         from .registry import make
 

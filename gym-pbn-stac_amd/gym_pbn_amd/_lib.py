@@ -107,6 +107,9 @@ class StateSetInfo(C.Structure):
 
 STATESET_MAX_STATES = 1 << 24
 
+# pbn_tenv_macro_device: modes (PBN_MACRO_*) and the cap on t_max (PBN_TENV_MACRO_MAX_T)
+from .macro_env import MACRO_INTERVAL, MACRO_TRIGGER, TENV_MACRO_MAX_T  # noqa: E402,F401
+
 _PP = C.POINTER(_vp)
 
 # name -> (restype, argtypes); mirrors include/pbn_abi.h one to one
@@ -179,6 +182,8 @@ SIGNATURES = {
     "pbn_stateset_lookup_device": (C.c_int, [_vp, _vp, _vp, _vp]),
     "pbn_tenv_step_device": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int, _vp, _vp, _vp, _vp]),
     "pbn_tenv_reset_device": (C.c_int, [_vp, _vp, C.c_uint64, _vp]),
+    "pbn_tenv_macro_device": (C.c_int, [_vp, _vp, C.c_int, C.c_uint32, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32,
+                                        C.c_int32, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 

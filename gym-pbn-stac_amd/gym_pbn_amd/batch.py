@@ -435,6 +435,23 @@ class PBNBatch:
         uniformly (Philox stream 9), node 0 cleared; asynchronous."""
         L.check(L.lib.pbn_tenv_reset_device(self._h, C.c_void_p(d_states), int(n_states), C.c_void_p(d_mask or None)))
 
+    def tenv_macro_device(self, target, mode: int, t_max: int, d_actions: int, d_limit: int, d_flags: int, *,
+                          d_reward_i32: int = 0, d_reward_f64: int = 0, d_gpow: int = 0, d_stop_thr: int = 0,
+                          d_obs: int = 0, d_interval: int = 0, d_first_hit: int = 0, d_labels: int = 0,
+                          reward_target: int = 20, step_cost: int = 4, action_cost: int = 1, check: bool = False):
+        """The macro step of ``PBNSampledDataEnv`` (``mode`` ``MACRO_INTERVAL``: ``d_limit`` rounds, int32 reward
+        sum) or ``PBNSelfTriggeringEnv`` (``MACRO_TRIGGER``: ``d_limit`` tenths of stop probability, at most
+        ``t_max`` rounds, float64 discounted sum over ``d_gpow``, stop compare against ``d_stop_thr``) of every env
+        in one launch, on device buffers: per round flip node ``a - 1`` (``a != 0``), one ``PBN.step`` update (the
+        draw ``step(1)`` would make), membership in ``target``, reward. ``update_count`` advances by ``t_max``.
+        Asynchronous unless ``check``."""
+        L.check(L.lib.pbn_tenv_macro_device(
+            self._h, target.handle, int(mode), int(t_max), C.c_void_p(d_actions), C.c_void_p(d_limit),
+            C.c_void_p(d_gpow or None), C.c_void_p(d_stop_thr or None), int(reward_target), int(step_cost),
+            int(action_cost), int(bool(check)), C.c_void_p(d_obs or None), C.c_void_p(d_reward_i32 or None),
+            C.c_void_p(d_reward_f64 or None), C.c_void_p(d_flags), C.c_void_p(d_interval or None),
+            C.c_void_p(d_first_hit or None), C.c_void_p(d_labels or None)))
+
     def synch_step(self, n_steps: int = 1, perturbation_prob: float = 0.0):
         """Synchronous update (base.py:286-303); perturbation_prob > 0 enables perturbations (p=0.001 there)."""
         gap = flip_gap_table(self.n_nodes, perturbation_prob)

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define PBN_ABI_VERSION 19
+#define PBN_ABI_VERSION 20
 
 enum {
     PBN_OK = 0,
@@ -424,6 +424,37 @@ int pbn_tenv_step_device(pbn_batch *b, const pbn_stateset *target, const int32_t
  * counter {0, reset_count, global env id}, row = mulhi(word 0, n_states); reset_count advances by 1 per call
  * (modulo 2^32). n_states == 0 or >= 2^32: PBN_E_INVALID. */
 int pbn_tenv_reset_device(pbn_batch *b, const uint64_t *d_states, uint64_t n_states, const uint8_t *d_mask);
+
+/* ---- the macro-action envs on the device: PBNSampledDataEnv.step (sampled_data.py:52-88) and
+ * PBNSelfTriggeringEnv.step (self_triggering.py:56-92) for every env in one launch ----
+ * PROB_TABLE batches only. Device arrays, asynchronous, on the batch's stream. Env e repeats, for i = 0, 1, ...:
+ * flip node a - 1 if a = d_actions[e] != 0 (both reference envs flip `action - 1`, so node 0 can be flipped here;
+ * PBN-v0 above flips node `action`); one PBN.step update with exactly the draw pbn_step would make for update
+ * update_count + i; terminated_i = state in target; r_i = terminated_i ? reward_target : -(step_cost + (a != 0 ?
+ * action_cost : 0)). After k rounds the state is what k rounds of pbn_flip (offset 1) + pbn_step(1) give.
+ *   PBN_MACRO_INTERVAL: d_limit[e] in [1, t_max] rounds; d_reward_i32[e] = the sum of r_i.
+ *   PBN_MACRO_TRIGGER:  d_limit[e] = p in [1, 10], the stop probability in tenths. The env stops after round i if
+ *     k53 <= d_stop_thr[p] or i + 1 == t_max, with k53 = (w0 >> 5) << 26 | w1 >> 6 from the Philox call of stream
+ *     10, counter {lo, hi of update_count + i, global env id}. d_stop_thr: 11 values floor((p / 10) * 2^53), entry 0
+ *     unused, which makes the compare the reference's uniform(0, 1) <= p / 10. d_reward_f64[e] = the sum of
+ *     d_gpow[i] * r_i accumulated in order from 0.0, one IEEE multiply and one IEEE add per round (never fused);
+ *     d_gpow: t_max doubles, gamma ** i. Both tables are the caller's device memory.
+ * The mode's reward array and its tables must be given, the other mode's may be NULL. d_flags [B]:
+ * PBN_FLAG_TERMINATED iff the LAST round's state is in the target (what the reference returns), never truncated.
+ * Optional (NULL to skip): d_obs [B][W] the final state, d_interval [B] the rounds run, d_first_hit [B] the first i
+ * with terminated_i or -1, d_labels [B] the target set's label of the final state.
+ * An env whose action is outside [0, N] or whose limit is outside its range is skipped whole -- state and outputs
+ * left as they were -- and noted in pbn_tenv_step_device's sticky flag; `check` as there.
+ * The batch's update counter advances by t_max, not by the longest run of rounds (which the host does not know),
+ * and also when an env was refused: the next call's draws stay disjoint from this one's, and the call mixes freely
+ * with pbn_step, pbn_flip and pbn_tenv_step_device. mode or t_max outside their range: PBN_E_INVALID. */
+enum { PBN_MACRO_INTERVAL = 0, PBN_MACRO_TRIGGER = 1 };
+#define PBN_TENV_MACRO_MAX_T 65536u
+int pbn_tenv_macro_device(pbn_batch *b, const pbn_stateset *target, int mode, uint32_t t_max, const int32_t *d_actions,
+                          const int32_t *d_limit, const double *d_gpow, const uint64_t *d_stop_thr,
+                          int32_t reward_target, int32_t step_cost, int32_t action_cost, int check, uint64_t *d_obs,
+                          int32_t *d_reward_i32, double *d_reward_f64, uint8_t *d_flags, int32_t *d_interval,
+                          int32_t *d_first_hit, int32_t *d_labels);
 
 #ifdef __cplusplus
 }
