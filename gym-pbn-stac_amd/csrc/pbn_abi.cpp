@@ -66,6 +66,9 @@ static Knobs read_knobs() {
     }
     if (const char* v = getenv("PBNSIM_MT_LANES")) k.mt_lane_walk = atoi(v) != 0;
     if (const char* v = getenv("PBNSIM_ROLL_GROUP")) k.roll_group = std::max(0, atoi(v));
+    if (const char* v = getenv("PBNSIM_ENVSET_GRID")) k.envset_grid = std::max(1, atoi(v));
+    if (const char* v = getenv("PBNSIM_ENVSET_NO_HULL")) k.envset_no_hull = atoi(v) != 0;
+    if (const char* v = getenv("PBNSIM_ENVSET_NO_SKIP")) k.envset_no_skip = atoi(v) != 0;
     return k;
 }
 

@@ -178,6 +178,10 @@ struct Knobs {
     int ssd_shared = -1;      // PBNSIM_SSD_SHARED: 0 = one wave per env, 4 / 8 = that many, 1 = the default
                               // count, -1 = by size
     bool mt_lane_walk = false;  // PBNSIM_MT_LANES=1: MT-mode steps of predictor-mix networks on k_mt_step
+    int envset_grid = 0;           // PBNSIM_ENVSET_GRID: cap on k_env_set's workgroups (tests: a small batch walks the
+                                   // grid-stride loop), 0 = by occupancy
+    bool envset_no_hull = false;   // PBNSIM_ENVSET_NO_HULL=1 (measurement): k_env_set without the hull pre-filter
+    bool envset_no_skip = false;   // PBNSIM_ENVSET_NO_SKIP=1 (measurement): k_env_set looks up after unchanged updates too
 };
 
 struct pbn_batch {
@@ -261,6 +265,10 @@ struct pbn_batch {
         int bpc = 0;     // k_tenv_step's resident workgroups per CU (0: not asked yet)
         int macro_bpc[2] = {0, 0};  // k_tenv_macro's, by mode
     } tenv;
+    struct EnvSet {      // the until-attractor env over a state set (pbn_abi_env_set.cpp)
+        DevBuf err;      // sticky flag of pbn_env_set_step_device / _reset_device, read and cleared by pbn_env_set_check
+        int bpc = 0;     // k_env_set's resident workgroups per CU (0: not asked yet)
+    } envset;
     // timing: mode 1 = an event pair around every launch; mode 2 = one region
     // (start before the first launch after enabling, stop after the latest launch)
     struct Timing {

@@ -419,8 +419,51 @@ struct TenvResetArgs {
     const uint8_t* mask;     // [B] or null
 };
 
+// The until-attractor multi-flip env over an exact labelled state set (k_env_set, pbn_env_set.hip):
+// k_env's env step with "attracting" read as "member of the set", a target label per env.
+struct EnvSetArgs {
+    uint64_t* state;         // [B][W]
+    int64_t* n_steps;        // [B]
+    const int32_t* actions;  // [B][A]
+    const void* img;         // network image (either kind)
+    NetLayout L;
+    uint64_t B, env_base, seed;
+    uint32_t call_idx, update_cap;
+    int32_t A, offset, dedup, horizon, reward_success, action_cost;
+    int32_t first_tested;    // 1: the state after the first update is tested, not the snapshot
+    SetView set;
+    uint64_t hull_all[MAX_WORDS], hull_any[MAX_WORDS];  // the set's AND / OR words (the first W are read)
+    int32_t always_lookup;   // measurement (PBNSIM_ENVSET_NO_SKIP): look up after unchanged updates too
+    int32_t target_label;    // the target of every env when target_labels is null
+    const int32_t* target_labels;  // [B] or null
+    uint64_t* obs;           // [B][W]
+    int32_t* reward;         // [B]
+    uint8_t* flags;          // [B]
+    uint32_t* n_updates;     // [B]
+    int32_t* labels;         // [B] or null
+    int32_t* error;          // sticky: set to 1 by an env whose action row names no node (the env is skipped)
+};
+
+struct EnvSetResetArgs {
+    uint64_t* state;
+    int64_t* n_steps;
+    uint64_t B, env_base, seed;
+    uint32_t reset_count;
+    const uint64_t* rows;      // [S][W], ordered by label
+    const uint32_t* row_off;   // [n_labels + 1]: attractor k's rows are row_off[k] .. row_off[k + 1] - 1
+    int32_t n_labels;
+    int32_t source_label;      // the source of every env when source_labels is null
+    const int32_t* source_labels;  // [B] or null
+    const uint8_t* mask;       // [B] or null
+    int32_t clear_node0;       // truth-table networks: node 0 cleared (pbn.py:118)
+    int32_t* error;            // EnvSetArgs::error: set to 1 by an env whose source names no non-empty attractor
+};
+
 // Launchers (pbn_step.hip, pbn_state.hip, pbn_env.hip, pbn_group.hip, pbn_mt.hip, pbn_ssd.hip, pbn_sync.hip, pbn_reach.hip,
-// pbn_tenv.hip, pbn_tenv_macro.hip). Return hipError_t as int.
+// pbn_tenv.hip, pbn_tenv_macro.hip, pbn_env_set.hip). Return hipError_t as int.
+int launch_env_set(int W, const EnvSetArgs& a, int grid, void* stream);
+int launch_env_set_reset(int W, const EnvSetResetArgs& a, void* stream);
+int max_blocks_env_set(int W, int kind, uint32_t image_bytes, int* blocks_per_cu);
 enum { REACH_K_UNSTABLE = 0, REACH_K_SEED, REACH_K_EXPAND, REACH_K_BACK_START, REACH_K_BACK, REACH_K_HULL };
 int launch_reach(int W, int which, const ReachArgs& a, int grid, void* stream);
 int launch_set_lookup(int W, const SetLookupArgs& a, void* stream);

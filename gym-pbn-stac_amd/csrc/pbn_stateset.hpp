@@ -102,9 +102,25 @@ struct StateSetTable {
     uint32_t slots = 0;
     uint32_t max_probe = 0;  // the longest walk of any member (1 = at home); 0 for the empty set
     uint64_t n_states = 0;   // distinct members
+    int32_t max_label = -1;  // the largest label (-1 for the empty set)
     std::vector<uint32_t> meta;
     std::vector<uint64_t> keys;
+    // AND / OR over the members' words ([W] each; the empty set: the N-bit mask / 0). care = ~(all ^ any) names the
+    // nodes every member agrees on: a state with (s ^ all) & care != 0 is no member (stateset_hull_rejects), which
+    // k_env_set (pbn_env_set.hip) tests before it touches the table.
+    std::vector<uint64_t> hull_all, hull_any;
 };
+
+// The hull pre-filter: true only for states that differ from every member in a node all members agree on.
+template <int W>
+PBN_HD bool stateset_hull_rejects(const uint64_t (&s)[W], const uint64_t (&all)[W], const uint64_t (&any)[W]) {
+    uint64_t d = 0;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int k = 0; k < W; ++k) d |= (s[k] ^ all[k]) & ~(all[k] ^ any[k]);
+    return d != 0;
+}
 
 enum {
     STATESET_OK = 0,
@@ -130,6 +146,10 @@ inline int stateset_build(int n_nodes, const uint64_t* states, const int32_t* la
     t->slots = stateset_slots(n_rows);
     t->max_probe = 0;
     t->n_states = 0;
+    t->max_label = -1;
+    t->hull_all.assign(W, ~0ull);
+    if (n_nodes & 63) t->hull_all[W - 1] = (1ull << (n_nodes & 63)) - 1ull;
+    t->hull_any.assign(W, 0ull);
     t->meta.assign(t->slots, 0u);
     t->keys.assign((size_t)t->slots * W, 0ull);
     const uint32_t mask = t->slots - 1u;
@@ -147,7 +167,12 @@ inline int stateset_build(int n_nodes, const uint64_t* states, const int32_t* la
                 if (t->meta[slot] == 0) {
                     t->meta[slot] = (uint32_t)label + 1u;
                     for (int k = 0; k < WW; ++k) t->keys[(size_t)slot * WW + k] = s[k];
+                    for (int k = 0; k < WW; ++k) {
+                        t->hull_all[k] &= s[k];
+                        t->hull_any[k] |= s[k];
+                    }
                     t->n_states++;
+                    if (label > t->max_label) t->max_label = label;
                     if (probe > t->max_probe) t->max_probe = probe;
                     break;
                 }

@@ -39,7 +39,7 @@ def __getattr__(name):
         from .stateset import StateSet
 
         return StateSet
-    if name in ("TorchVecPBNEnv", "TorchVecPBNTargetMultiEnv"):
+    if name in ("TorchVecPBNEnv", "TorchVecPBNTargetMultiEnv", "TorchVecPBNTargetMultiSetEnv"):
         from . import torch_env
 
         return getattr(torch_env, name)

@@ -184,6 +184,11 @@ SIGNATURES = {
     "pbn_tenv_reset_device": (C.c_int, [_vp, _vp, C.c_uint64, _vp]),
     "pbn_tenv_macro_device": (C.c_int, [_vp, _vp, C.c_int, C.c_uint32, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32,
                                         C.c_int32, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pbn_stateset_get_hull": (C.c_int, [_vp, _u64p, _u64p, _i32p]),
+    "pbn_env_set_step_device": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int32, C.c_int32,
+                                          C.c_int32, C.c_int, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pbn_env_set_reset_device": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, _vp, _vp]),
+    "pbn_env_set_check": (C.c_int, [_vp]),
 }
 
 

@@ -452,6 +452,38 @@ class PBNBatch:
             C.c_void_p(d_reward_f64 or None), C.c_void_p(d_flags), C.c_void_p(d_interval or None),
             C.c_void_p(d_first_hit or None), C.c_void_p(d_labels or None)))
 
+    # -- the until-attractor env over a labelled state set (torch_env.TorchVecPBNTargetMultiSetEnv) --------
+    def env_set_step_device(self, stateset, d_actions: int, A: int, d_obs: int, d_reward: int, d_flags: int,
+                            d_n_updates: int, d_labels: int = 0, *, target_label: int = 0, d_target_labels: int = 0,
+                            offset: int = 1, dedup: bool = True, update_cap: int = 1 << 20, horizon: int = 100,
+                            reward_success: int = 1000, action_cost: int = 1, first_update_tested: bool = False):
+        """:meth:`env_step_multi_device` (``pbn_target_multi.py:119-154``, the same draws and call counter) with
+        "attracting" read as "member of ``stateset``" (label = the attractor's index) and the target as a label:
+        ``d_target_labels`` (device int32 ``[B]``) or ``target_label`` for every env. ``d_labels`` (optional, int32
+        ``[B]``) receives the label each env landed in, -1 when the update cap ended its loop. Asynchronous; a row
+        with an action that names no node leaves its env untouched and is reported by :meth:`env_set_check`."""
+        L.check(L.lib.pbn_env_set_step_device(
+            self._h, stateset.handle, C.c_void_p(d_actions), int(A), int(bool(dedup)), int(offset), int(update_cap),
+            int(horizon), int(reward_success), int(action_cost), int(bool(first_update_tested)), int(target_label),
+            C.c_void_p(d_target_labels or None), C.c_void_p(d_obs), C.c_void_p(d_reward), C.c_void_p(d_flags),
+            C.c_void_p(d_n_updates), C.c_void_p(d_labels or None)))
+
+    def env_set_reset_device(self, d_rows: int, d_row_off: int, n_labels: int, source_label: int = 0,
+                             d_source_labels: int = 0, d_mask: int = 0):
+        """Envs with ``d_mask[e] != 0`` (0 = all) take a row of their source attractor, drawn uniformly (Philox
+        stream 9), and ``n_steps = 0``; node 0 is cleared for truth-table networks. ``d_rows``: device ``[S][W]``
+        ordered by label; ``d_row_off``: device uint32 ``[n_labels + 1]``; the source is ``d_source_labels[e]``
+        (device int32 ``[B]``) or ``source_label``. Asynchronous; an env whose source names no non-empty attractor
+        is left untouched and reported by :meth:`env_set_check`."""
+        L.check(L.lib.pbn_env_set_reset_device(self._h, C.c_void_p(d_rows), C.c_void_p(d_row_off), int(n_labels),
+                                               int(source_label), C.c_void_p(d_source_labels or None),
+                                               C.c_void_p(d_mask or None)))
+
+    def env_set_check(self):
+        """Waits for the stream; ``ValueError`` if :meth:`env_set_step_device` or :meth:`env_set_reset_device`
+        skipped an env since the last check (reported once)."""
+        L.check(L.lib.pbn_env_set_check(self._h))
+
     def synch_step(self, n_steps: int = 1, perturbation_prob: float = 0.0):
         """Synchronous update (base.py:286-303); perturbation_prob > 0 enables perturbations (p=0.001 there)."""
         gap = flip_gap_table(self.n_nodes, perturbation_prob)

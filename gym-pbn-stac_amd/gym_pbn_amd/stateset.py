@@ -66,6 +66,22 @@ class StateSet:
     def __len__(self) -> int:
         return int(self.info()["n_states"])
 
+    def hull(self):
+        """``(all_words, any_words)``: the AND and the OR of the members' words, ``[W]`` uint64 each. Node ``i`` has
+        one value in every member iff bit ``i`` of ``all ^ any`` is 0: what the until-attractor kernel tests before
+        it probes the table."""
+        a = np.empty(self.n_words, dtype=np.uint64)
+        o = np.empty(self.n_words, dtype=np.uint64)
+        L.check(L.lib.pbn_stateset_get_hull(self._h, L.ptr(a, L._u64p), L.ptr(o, L._u64p), None))
+        return a, o
+
+    @property
+    def n_labels(self) -> int:
+        """The largest label + 1 (0 for the empty set)."""
+        top = C.c_int32(-1)
+        L.check(L.lib.pbn_stateset_get_hull(self._h, None, None, C.byref(top)))
+        return int(top.value) + 1
+
     def lookup(self, states) -> np.ndarray:
         """Labels ``[n]`` int32 of packed ``states`` ``[n][W]`` on the host (-1: not a member)."""
         w = np.ascontiguousarray(states, dtype=np.uint64).reshape(-1, self.n_words)

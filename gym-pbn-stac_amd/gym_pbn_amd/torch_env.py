@@ -306,4 +306,184 @@ class TorchVecPBNEnv:
         self.target.close()
 
 
-__all__ = ["TorchVecPBNTargetMultiEnv", "TorchVecPBNEnv"]
+def labelled_attractors(network, attractors, net=None, device: int = 0, seed: int = 0):
+    """``attractors`` in any form :class:`TorchVecPBNTargetMultiSetEnv` accepts -> ``(rows, labels, row_off)``: the
+    attractors' states as packed ``[S][W]`` uint64 rows ordered by label (= the attractor's index), their labels
+    ``[S]`` int32 and ``row_off`` ``[K + 1]`` uint32, attractor ``k`` owning rows ``row_off[k] .. row_off[k + 1] - 1``.
+    Host only unless ``attractors == "find"`` (which needs ``net`` and a device).
+
+    An attractor given as cube tuples (ints and ``'*'``) is expanded (``expand_cubes``, overlapping cubes united);
+    the expansion is counted first and refused with ``ValueError`` when the set would pass ``STATESET_MAX_STATES``."""
+    import numpy as np
+
+    from .attractors import AttractorResult, expand_cubes
+
+    N = network.n_nodes
+    if attractors is None:
+        raise ValueError("attractors: an AttractorResult, \"find\", or a list of attractors")
+    if not isinstance(attractors, (str, AttractorResult)):
+        items, total = [], 0
+        for a in attractors:
+            if not isinstance(a, np.ndarray) and any(v == "*" for c in a for v in c):
+                total += sum(1 << sum(1 for v in c if v == "*") for c in a)
+                if total > L.STATESET_MAX_STATES:
+                    raise ValueError(f"the cubes expand to more than STATESET_MAX_STATES = {L.STATESET_MAX_STATES} "
+                                     "states; keep them as cubes (TorchVecPBNTargetMultiEnv)")
+                a = np.unique(expand_cubes([tuple(c) for c in a], N), axis=0)
+            items.append(a)
+        attractors = items
+    packed = _packed_attractors(network, net, attractors, device, seed)
+    rows = np.ascontiguousarray(np.concatenate(packed), dtype=np.uint64)
+    if len(rows) > L.STATESET_MAX_STATES:
+        raise ValueError(f"{len(rows)} attracting states: more than STATESET_MAX_STATES = {L.STATESET_MAX_STATES}")
+    labels = np.concatenate([np.full(len(a), k, np.int32) for k, a in enumerate(packed)])
+    row_off = np.concatenate([[0], np.cumsum([len(a) for a in packed])]).astype(np.uint32)
+    return rows, labels, row_off
+
+
+class TorchVecPBNTargetMultiSetEnv:
+    """:class:`TorchVecPBNTargetMultiEnv` over attractors given as exact state lists: one labelled
+    :class:`~gym_pbn_amd.stateset.StateSet` (label = the attractor's index) takes the place of the cubes, so an
+    attractor may have any shape and up to ``2**24`` states in all, ``info["label"]`` says which attractor each env
+    landed in, and every env has a source attractor (where ``reset`` puts it) and a target attractor (where
+    ``terminated`` is raised) of its own -- the ``state_attractor_id, target_attractor_id`` the reference's ``reset``
+    draws per episode (``pbn_target_multi.py:232-235``). The defaults are what the reference then does: source
+    attractor 0, target attractor ``K - 1``.
+
+    ``network``: a bundled name, a ``PredictorNetwork``, a ``TruthTableNetwork`` or a ``Net``. ``attractors``: an
+    :class:`~gym_pbn_amd.attractors.AttractorResult`; ``"find"``; or a list of attractors, each a packed ``[S][W]``
+    uint64 array, a list of state tuples, or a list of cube tuples (expanded; refused past ``2**24`` states).
+
+    ``step`` is one launch (``pbn_env_set_step_device``) with the same draws as ``TorchVecPBNTargetMultiEnv`` for the
+    same seed; ``reset`` draws a state of the source attractor on the device (Philox stream 9, as ``TorchVecPBNEnv``).
+    """
+
+    def __init__(self, network, attractors, n_envs: int, horizon: int = 100, device: int = 0, seed: int = 0,
+                 env_id_base: int = 0, update_cap: int = 1 << 20, auto_reset: bool = False,
+                 reward_success: int = 1000, action_cost: int = 1):
+        import numpy as np
+        import torch
+
+        from .network import TruthTableNetwork
+        from .stateset import StateSet
+
+        if not isinstance(network, (PredictorNetwork, TruthTableNetwork, Net)):
+            network = load_network(network)
+        self.net = network if isinstance(network, Net) else Net(network)
+        self.network = self.net.network
+        self.num_envs = int(n_envs)
+        self.N, self.W = self.net.n_nodes, self.net.n_words
+        self.device = torch.device("cuda", device)
+        rows, labels, row_off = labelled_attractors(self.network, attractors, self.net, device, seed)
+        self.n_attractors = len(row_off) - 1
+        self.row_off = row_off
+        self.set = StateSet(rows, self.N, labels=labels, device=device)
+        self.horizon, self.update_cap = int(horizon), int(update_cap)
+        self.reward_success, self.action_cost = int(reward_success), int(action_cost)
+        self.auto_reset = bool(auto_reset)
+        self.batch = PBNBatch(self.net, self.num_envs, device=device, env_id_base=env_id_base, seed=seed)
+        self.observation_space = spaces.MultiBinary(self.N)  # pbn_target_multi.py:56-59
+        self.action_space = spaces.MultiDiscrete(self.N + 1)
+        B = self.num_envs
+        with torch.cuda.device(self.device):
+            # uploaded once: the table reset and auto-reset draw from
+            self._rows = torch.from_numpy(rows.view(np.int64)).to(self.device).contiguous()
+            self._row_off = torch.from_numpy(row_off.view(np.int32)).to(self.device).contiguous()
+            self.source = torch.zeros(B, dtype=torch.int32, device=self.device)
+            self.target = torch.full((B,), self.n_attractors - 1, dtype=torch.int32, device=self.device)
+            self._flags = torch.empty(B, dtype=torch.uint8, device=self.device)
+        self._use_stream()
+
+    _use_stream = TorchVecPBNTargetMultiEnv._use_stream
+    _bits = TorchVecPBNTargetMultiEnv._bits
+
+    def observation_words(self):
+        import torch
+
+        self._use_stream()
+        words = torch.empty((self.num_envs, self.W), dtype=torch.int64, device=self.device)
+        self.batch.get_state_device(words.data_ptr())
+        return words
+
+    def _assign(self, held, value, m):
+        """``held[e] = value[e]`` (an int or a device int tensor ``[B]``) for the envs of mask ``m`` (None: all)."""
+        import torch
+
+        if value is None:
+            return
+        if torch.is_tensor(value):
+            v = value.to(device=self.device, dtype=torch.int32).reshape(-1)
+            if v.shape[0] != self.num_envs:
+                raise ValueError(f"labels for {v.shape[0]} envs, the batch has {self.num_envs}")
+        else:
+            if not 0 <= int(value) < self.n_attractors:
+                raise ValueError(f"attractor {value} outside [0, {self.n_attractors})")
+            v = torch.full_like(held, int(value))
+        if m is None:
+            held.copy_(v)
+        else:
+            held.copy_(torch.where(m != 0, v, held))
+
+    def _reset(self, m):
+        self.batch.env_set_reset_device(self._rows.data_ptr(), self._row_off.data_ptr(), self.n_attractors,
+                                        d_source_labels=self.source.data_ptr(),
+                                        d_mask=0 if m is None else m.data_ptr())
+
+    def reset(self, mask=None, source=None, target=None):
+        """Every env (``mask`` None) or the envs where the device bool / uint8 ``mask`` is set take a state drawn
+        uniformly from their source attractor and ``n_steps = 0``. ``source`` / ``target``: an int or a device int
+        tensor ``[B]`` of attractor indices, stored for the envs being reset and kept until their next reset that
+        names one. An env whose source is no attractor is left as it is (``batch.env_set_check()`` reports it).
+        Returns observations ``[B][N]`` uint8 on the device."""
+        import torch
+
+        self._use_stream()
+        m = None if mask is None else mask.to(device=self.device, dtype=torch.uint8).contiguous()
+        self._assign(self.source, source, m)
+        self._assign(self.target, target, m)
+        self._reset(m)
+        return self._bits()
+
+    def step(self, actions):
+        """``actions``: int tensor ``[B]`` or ``[B][A]`` of node + 1 values (0 = none), on the GPU. Returns ``(obs
+        [B][N] uint8, reward [B] int32, terminated [B] bool, truncated [B] bool, info)`` as device tensors; ``info``
+        holds ``n_updates``, ``capped``, ``obs_words`` and ``label`` (the attractor the env landed in, -1 when
+        capped); ``terminated`` is ``label == target`` of the env."""
+        import torch
+
+        a = actions
+        if a.dim() == 1:
+            a = a.unsqueeze(1)
+        a = a.to(device=self.device, dtype=torch.int32).contiguous()
+        if a.shape[0] != self.num_envs:
+            raise ValueError(f"actions for {a.shape[0]} envs, the batch has {self.num_envs}")
+        self._use_stream()
+        B = self.num_envs
+        words = torch.empty((B, self.W), dtype=torch.int64, device=self.device)
+        reward = torch.empty(B, dtype=torch.int32, device=self.device)
+        nup = torch.empty(B, dtype=torch.int32, device=self.device)
+        label = torch.empty(B, dtype=torch.int32, device=self.device)
+        self.batch.env_set_step_device(self.set, a.data_ptr(), a.shape[1], words.data_ptr(), reward.data_ptr(),
+                                       self._flags.data_ptr(), nup.data_ptr(), label.data_ptr(),
+                                       d_target_labels=self.target.data_ptr(), offset=1, dedup=True,
+                                       update_cap=self.update_cap, horizon=self.horizon,
+                                       reward_success=self.reward_success, action_cost=self.action_cost)
+        flags = self._flags
+        term = (flags & L.FLAG_TERMINATED) != 0
+        trunc = (flags & L.FLAG_TRUNCATED) != 0
+        info = {"n_updates": nup, "capped": (flags & L.FLAG_CAPPED) != 0, "obs_words": words, "label": label}
+        obs = self._bits(words)
+        if self.auto_reset:
+            self._reset((term | trunc).to(torch.uint8).contiguous())
+        return obs, reward, term, trunc, info
+
+    def close(self):
+        import torch
+
+        torch.cuda.current_stream(self.device).synchronize()
+        self.batch.set_stream(None)
+        self.batch.close()
+        self.set.close()
+
+
+__all__ = ["TorchVecPBNTargetMultiEnv", "TorchVecPBNEnv", "TorchVecPBNTargetMultiSetEnv", "labelled_attractors"]

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define PBN_ABI_VERSION 20
+#define PBN_ABI_VERSION 21
 
 enum {
     PBN_OK = 0,
@@ -455,6 +455,48 @@ int pbn_tenv_macro_device(pbn_batch *b, const pbn_stateset *target, int mode, ui
                           int32_t reward_target, int32_t step_cost, int32_t action_cost, int check, uint64_t *d_obs,
                           int32_t *d_reward_i32, double *d_reward_f64, uint8_t *d_flags, int32_t *d_interval,
                           int32_t *d_first_hit, int32_t *d_labels);
+
+/* ---- the until-attractor multi-flip env over an exact labelled state set: PBNTargetMultiEnv.step
+ * (pbn_target_multi.py:119-154) with `tuple(state) in self.attracting_states` (:437-455, :489-492) as membership in
+ * a pbn_stateset whose label is the attractor's index, and the target attractor chosen per env (the reference's
+ * reset draws target_attractor_id per episode, :232-235) ----
+ * Both network kinds. Device arrays, asynchronous, on the batch's stream; one launch per call.
+ *
+ * The set's hull (pbn_reach_hull's convention): all_words / any_words [W] = AND / OR over the members (the empty set:
+ * the N-bit mask and 0); *max_label = the largest label (-1: the empty set). Any of the three may be NULL. */
+int pbn_stateset_get_hull(const pbn_stateset *s, uint64_t *all_words, uint64_t *any_words, int32_t *max_label);
+/* Per env exactly pbn_env_step_multi_device's step (same arguments, same draws: Philox stream 3, counter {update >> 1,
+ * env_call_count, global env id}; env_call_count advances by 1, so the two calls interleave freely), with "matches
+ * some cube" read as "is a member of set": n_steps += 1; the flips of row d_actions[e] (A values, offset, dedup,
+ * Python indexing); obs = the state after the flips; updates until the tested state is a member or update_cap updates
+ * were made -- after update 1 the observation before the update is tested (:134; first_update_tested != 0: the state
+ * after it, PBNTargetEnv.step), from update 2 on the state itself. Outputs: d_obs [B][W] the state tested last,
+ * d_labels [B] (may be NULL) the set's label of it or -1 when the cap ended the loop, d_flags PBN_FLAG_TERMINATED iff
+ * that label equals the env's target -- d_target_labels[e], or target_label for every env when d_target_labels is
+ * NULL -- | PBN_FLAG_TRUNCATED iff n_steps == horizon | PBN_FLAG_CAPPED, d_reward = (terminated ? reward_success : 0)
+ * - action_cost * (dedup ? distinct actions : A), d_n_updates the updates made.
+ * An env whose row holds an action that names no node is skipped whole, as pbn_env_step_multi_device skips it --
+ * state, n_steps and outputs left as they were -- and noted in a sticky device flag (pbn_env_set_check).
+ * PBN_E_INVALID, before anything is launched or any counter moves: A < 1 (or > 4096, offset not 0 / 1), a set of
+ * another n_nodes or device, a host-only set, target_label outside [0, the set's largest label] with d_target_labels NULL. */
+int pbn_env_set_step_device(pbn_batch *b, const pbn_stateset *set, const int32_t *d_actions, int A, int dedup,
+                            int offset, uint32_t update_cap, int32_t horizon, int32_t reward_success,
+                            int32_t action_cost, int first_update_tested, int32_t target_label,
+                            const int32_t *d_target_labels, uint64_t *d_obs, int32_t *d_reward, uint8_t *d_flags,
+                            uint32_t *d_n_updates, int32_t *d_labels);
+/* PBNTargetMultiEnv.reset (:227-259) over state lists: envs with d_mask[e] != 0 (NULL = all) take a state drawn
+ * uniformly from their source attractor (the reference's state_attractor_id, :232-235) -- d_source_labels[e], or
+ * source_label for every env when d_source_labels is NULL -- and n_steps = 0. d_rows [S][W] (device, 16-byte aligned)
+ * holds the attractors' states ordered by label, d_row_off [n_labels + 1] uint32 (device) the first row of each.
+ * Draw: Philox stream 9, counter {0, reset_count, global env id}, row = d_row_off[src] + mulhi(word 0, rows of src);
+ * node 0 is cleared for PROB_TABLE networks only (PBN.reset, pbn.py:118). reset_count advances by 1 per call. An env
+ * whose source is outside [0, n_labels) or names an attractor without rows is left untouched and noted in the sticky
+ * flag. n_labels < 1: PBN_E_INVALID. */
+int pbn_env_set_reset_device(pbn_batch *b, const uint64_t *d_rows, const uint32_t *d_row_off, int32_t n_labels,
+                             int32_t source_label, const int32_t *d_source_labels, const uint8_t *d_mask);
+/* Waits for the batch's stream; PBN_E_RANGE if an env was skipped by either call since the last check (the flag is
+ * cleared: reported once). */
+int pbn_env_set_check(pbn_batch *b);
 
 #ifdef __cplusplus
 }
