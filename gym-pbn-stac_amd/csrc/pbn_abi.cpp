@@ -459,22 +459,14 @@ int pbn_flip_device(pbn_batch* b, const int32_t* d_actions, int A, int offset, i
     CHECK_NN(d_actions, "d_actions");
     if (int rc = check_action_shape(A, offset)) return rc;
     SET_DEV(b);
-    int32_t* flag = (int32_t*)b->s_flip_err.p;  // zeroed at allocation and after every check
-    if (!flag) {
-        if (int rc = b->s_flip_err.ensure(4)) return rc;
-        flag = (int32_t*)b->s_flip_err.p;
-        HIP_TRY(hipMemsetAsync(flag, 0, 4, b->stream));
-    }
+    int32_t* flag = nullptr;
+    if (int rc = b->s_flip_err.get(b->stream, &flag)) return rc;
     FlipArgs a{b->d_state, d_actions, b->B, A, offset, dedup ? 1 : 0, b->N, flag};
     int e = launch_flip(b->W, a, b->grid_all(b->B), b->stream);
     if (e) return fail(PBN_E_HIP, "k_flip launch: %s", hipGetErrorString((hipError_t)e));
     if (!check) return 0;
-    if (!b->pin.ready()) return fail(PBN_E_NOMEM, "pinned staging buffer");
-    HIP_TRY(hipMemcpyAsync(b->pin.p, flag, 4, hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipMemsetAsync(flag, 0, 4, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
     int32_t err;
-    memcpy(&err, b->pin.p, 4);
+    if (int rc = b->s_flip_err.read_and_clear(b, &err)) return rc;
     if (err) return fail(PBN_E_RANGE, "Invalid action: a value names no node (rows holding one were left untouched)");
     return 0;
 }

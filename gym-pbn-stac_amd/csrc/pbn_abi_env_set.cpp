@@ -2,16 +2,6 @@
 // points over the kernels of pbn_env_set.hip. DESIGN.md §14.
 #include "pbn_host.hpp"
 
-// The sticky flag of k_env_set / k_env_set_reset: zeroed at allocation and after every pbn_env_set_check.
-static int env_set_error_flag(pbn_batch* b, int32_t** flag) {
-    if (!b->envset.err.p) {
-        if (int rc = b->envset.err.ensure(4)) return rc;
-        HIP_TRY(hipMemsetAsync(b->envset.err.p, 0, 4, b->stream));
-    }
-    *flag = (int32_t*)b->envset.err.p;
-    return 0;
-}
-
 extern "C" {
 
 int pbn_stateset_get_hull(const pbn_stateset* s, uint64_t* all_words, uint64_t* any_words, int32_t* max_label) {
@@ -35,31 +25,21 @@ int pbn_env_set_step_device(pbn_batch* b, const pbn_stateset* set, const int32_t
     CHECK_NN(d_flags, "d_flags");
     CHECK_NN(d_n_updates, "d_n_updates");
     if (int rc = check_action_shape(A, offset)) return rc;
-    if (set->device < 0) return fail(PBN_E_INVALID, "the state set is host-only (created with device -1)");
-    if (set->device != b->device)
-        return fail(PBN_E_INVALID, "the state set lives on device %d, the batch on device %d", set->device, b->device);
-    if (set->t.n_nodes != b->N)
-        return fail(PBN_E_INVALID, "the state set holds states of %d nodes, the batch has %d", set->t.n_nodes, b->N);
+    if (int rc = check_set_for_batch(b, set, "the state set", PBN_E_INVALID)) return rc;
     if (!d_target_labels && (target_label < 0 || target_label > set->t.max_label))
         return fail(PBN_E_INVALID, "target_label=%d outside the set's labels [0, %d]", (int)target_label,
                     (int)set->t.max_label);
-    if (b->net->kind == PBN_KIND_PROB_TABLE && b->N < 2)
-        return fail(PBN_E_UNSUPPORTED, "PBN.step updates a node in [1, N-1]: the network needs two nodes");
+    if (b->net->kind == PBN_KIND_PROB_TABLE)
+        if (int rc = check_two_nodes(b)) return rc;
     SET_DEV(b);
-    int32_t* flag;
-    if (int rc = env_set_error_flag(b, &flag)) return rc;
-    if (!b->envset.bpc)
-        if (int e = max_blocks_env_set(b->W, b->net->kind, b->net->L.bytes, &b->envset.bpc))
-            return fail(PBN_E_HIP, "occupancy query: %s", hipGetErrorString((hipError_t)e));
+    int32_t* flag = nullptr;
+    if (int rc = b->envset.err.get(b->stream, &flag)) return rc;
+    void* kernel = env_set_kernel(b->W, b->net->kind);
+    if (int rc = cached_bpc(b->envset.bpc, kernel, b->W, b->net->L.bytes)) return rc;
     EnvSetArgs a{};
-    a.state = b->d_state;
+    fill_lane_env(b, a);
     a.n_steps = b->d_nsteps;
     a.actions = d_actions;
-    a.img = b->d_image;
-    a.L = b->net->L;
-    a.B = b->B;
-    a.env_base = b->env_base;
-    a.seed = b->seed;
     a.call_idx = b->r6.calls;
     a.update_cap = update_cap;
     a.A = A;
@@ -84,9 +64,7 @@ int pbn_env_set_step_device(pbn_batch* b, const pbn_stateset* set, const int32_t
     a.n_updates = d_n_updates;
     a.labels = d_labels;
     a.error = flag;
-    int grid = b->grid_for(b->B, b->envset.bpc);
-    if (b->knob.envset_grid > 0) grid = std::min(grid, b->knob.envset_grid);
-    if (int rc = timed_launch(b, "k_env_set", [&] { return launch_env_set(b->W, a, grid, b->stream); })) return rc;
+    if (int rc = launch_lane_env_step(b, "k_env_set", kernel, a.L.bytes, b->envset.bpc, a)) return rc;
     b->r6.calls++;  // as pbn_env_step_multi_device: one env step launched
     return 0;
 }
@@ -98,8 +76,8 @@ int pbn_env_set_reset_device(pbn_batch* b, const uint64_t* d_rows, const uint32_
     CHECK_NN(d_row_off, "d_row_off");
     if (n_labels < 1) return fail(PBN_E_INVALID, "n_labels=%d: at least one attractor", (int)n_labels);
     SET_DEV(b);
-    int32_t* flag;
-    if (int rc = env_set_error_flag(b, &flag)) return rc;
+    int32_t* flag = nullptr;
+    if (int rc = b->envset.err.get(b->stream, &flag)) return rc;
     EnvSetResetArgs a{};
     a.state = b->d_state;
     a.n_steps = b->d_nsteps;
@@ -123,14 +101,8 @@ int pbn_env_set_reset_device(pbn_batch* b, const uint64_t* d_rows, const uint32_
 int pbn_env_set_check(pbn_batch* b) {
     CHECK_NN(b, "batch");
     SET_DEV(b);
-    int32_t* flag;
-    if (int rc = env_set_error_flag(b, &flag)) return rc;
-    if (!b->pin.ready()) return fail(PBN_E_NOMEM, "pinned staging buffer");
-    HIP_TRY(hipMemcpyAsync(b->pin.p, flag, 4, hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipMemsetAsync(flag, 0, 4, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
     int32_t err;
-    memcpy(&err, b->pin.p, 4);
+    if (int rc = b->envset.err.read_and_clear(b, &err)) return rc;
     if (err)
         return fail(PBN_E_RANGE, "Invalid action or source attractor: an env step or reset was skipped (envs holding "
                                  "one were left untouched)");

@@ -1,46 +1,16 @@
 // pbn_abi_tenv.cpp -- exact state sets (pbn_stateset_*), the PBN-v0 env and the macro-action envs on the device
 // (pbn_tenv_*): the entry points over pbn_stateset.hpp (the set's one definition) and the kernels of pbn_tenv.hip
-// and pbn_tenv_macro.hip.
+// and pbn_tenv_macro.hip (the reset: k_env_set_reset, pbn_env_set.hip).
 #include "pbn_host.hpp"
 
 static_assert((int)PBN_MACRO_INTERVAL == (int)TENV_MACRO_INTERVAL && (int)PBN_MACRO_TRIGGER == (int)TENV_MACRO_TRIGGER &&
                   PBN_TENV_MACRO_MAX_T == TENV_MACRO_MAX_T,
               "pbn_abi.h and pbn_params.hpp name the same modes and cap");
 
-// The set can serve this batch's launches: uploaded, on the batch's device, over states of the batch's width.
-static int check_set_for_batch(const pbn_batch* b, const pbn_stateset* s, const char* what) {
-    if (s->device < 0) return fail(PBN_E_STATE, "%s is a host-only state set (created with device -1)", what);
-    if (s->device != b->device)
-        return fail(PBN_E_INVALID, "%s lives on device %d, the batch on device %d", what, s->device, b->device);
-    if (s->t.n_nodes != b->N)
-        return fail(PBN_E_INVALID, "%s holds states of %d nodes, the batch has %d", what, s->t.n_nodes, b->N);
-    return 0;
-}
-
 static int check_table_batch(const pbn_batch* b, const char* fn) {
     if (b->net->kind != PBN_KIND_PROB_TABLE)
         return fail(PBN_E_UNSUPPORTED, "%s steps the PBN-v0 env of a truth-table network; this batch holds a "
                                        "predictor-mix network (its env is pbn_env_step_multi)", fn);
-    return 0;
-}
-
-// The sticky range flag of the env kernels (k_tenv_step, k_tenv_macro): zeroed at allocation and after every check.
-static int tenv_error_flag(pbn_batch* b, int32_t** flag) {
-    if (!b->tenv.err.p) {
-        if (int rc = b->tenv.err.ensure(4)) return rc;
-        HIP_TRY(hipMemsetAsync(b->tenv.err.p, 0, 4, b->stream));
-    }
-    *flag = (int32_t*)b->tenv.err.p;
-    return 0;
-}
-
-// Waits for the batch's stream, reads the flag and clears it.
-static int tenv_read_error_flag(pbn_batch* b, int32_t* flag, int32_t* err) {
-    if (!b->pin.ready()) return fail(PBN_E_NOMEM, "pinned staging buffer");
-    HIP_TRY(hipMemcpyAsync(b->pin.p, flag, 4, hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipMemsetAsync(flag, 0, 4, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    memcpy(err, b->pin.p, 4);
     return 0;
 }
 
@@ -127,7 +97,7 @@ int pbn_stateset_lookup_device(pbn_batch* b, const pbn_stateset* s, const void* 
     CHECK_NN(b, "batch");
     CHECK_NN(s, "stateset");
     CHECK_NN(d_labels, "d_labels");
-    if (int rc = check_set_for_batch(b, s, "the state set")) return rc;
+    if (int rc = check_set_for_batch(b, s, "the state set", PBN_E_STATE)) return rc;
     SET_DEV(b);
     SetLookupArgs a{d_words ? (const uint64_t*)d_words : b->d_state, s->view(), b->B, d_labels};
     return timed_launch(b, "k_set_lookup", [&] { return launch_set_lookup(b->W, a, b->stream); });
@@ -142,21 +112,15 @@ int pbn_tenv_step_device(pbn_batch* b, const pbn_stateset* target, const int32_t
     CHECK_NN(d_reward, "d_reward");
     CHECK_NN(d_flags, "d_flags");
     if (int rc = check_table_batch(b, "pbn_tenv_step_device")) return rc;
-    if (int rc = check_set_for_batch(b, target, "the target set")) return rc;
-    if (b->N < 2) return fail(PBN_E_UNSUPPORTED, "PBN.step updates a node in [1, N-1]: the network needs two nodes");
+    if (int rc = check_set_for_batch(b, target, "the target set", PBN_E_STATE)) return rc;
+    if (int rc = check_two_nodes(b)) return rc;
     SET_DEV(b);
-    int32_t* flag;
-    if (int rc = tenv_error_flag(b, &flag)) return rc;
-    if (!b->tenv.bpc)
-        if (int e = max_blocks_tenv(b->W, b->net->L.plane_off, &b->tenv.bpc))
-            return fail(PBN_E_HIP, "occupancy query: %s", hipGetErrorString((hipError_t)e));
+    int32_t* flag = nullptr;
+    if (int rc = b->tenv.err.get(b->stream, &flag)) return rc;
+    void* kernel = tenv_step_kernel(b->W);
+    if (int rc = cached_bpc(b->tenv.bpc, kernel, b->W, b->net->L.plane_off)) return rc;
     TenvArgs a{};
-    a.state = b->d_state;
-    a.img = b->d_image;
-    a.L = b->net->L;
-    a.B = b->B;
-    a.env_base = b->env_base;
-    a.seed = b->seed;
+    fill_lane_env(b, a);
     a.update = b->update_count;
     a.actions = d_actions;
     a.target = target->view();
@@ -168,12 +132,11 @@ int pbn_tenv_step_device(pbn_batch* b, const pbn_stateset* target, const int32_t
     a.flags = d_flags;
     a.labels = d_labels;
     a.error = flag;
-    const int grid = b->grid_for(b->B, b->tenv.bpc);
-    if (int rc = timed_launch(b, "k_tenv_step", [&] { return launch_tenv_step(b->W, a, grid, b->stream); })) return rc;
+    if (int rc = launch_lane_env_step(b, "k_tenv_step", kernel, a.L.plane_off, b->tenv.bpc, a)) return rc;
     b->update_count++;  // the launch happened: the count advances whether or not an action was refused
     if (!check) return 0;
     int32_t err;
-    if (int rc = tenv_read_error_flag(b, flag, &err)) return rc;
+    if (int rc = b->tenv.err.read_and_clear(b, &err)) return rc;
     if (err) return fail(PBN_E_RANGE, "Invalid action: a value outside [0, %d] (envs holding one were left untouched)", b->N - 1);
     return 0;
 }
@@ -202,22 +165,16 @@ int pbn_tenv_macro_device(pbn_batch* b, const pbn_stateset* target, int mode, ui
         return fail(PBN_E_INVALID, "t_max=%u outside [1, PBN_TENV_MACRO_MAX_T = %u]", (unsigned)t_max,
                     (unsigned)PBN_TENV_MACRO_MAX_T);
     if (int rc = check_table_batch(b, "pbn_tenv_macro_device")) return rc;
-    if (int rc = check_set_for_batch(b, target, "the target set")) return rc;
-    if (b->N < 2) return fail(PBN_E_UNSUPPORTED, "PBN.step updates a node in [1, N-1]: the network needs two nodes");
+    if (int rc = check_set_for_batch(b, target, "the target set", PBN_E_STATE)) return rc;
+    if (int rc = check_two_nodes(b)) return rc;
     SET_DEV(b);
-    int32_t* flag;
-    if (int rc = tenv_error_flag(b, &flag)) return rc;
+    int32_t* flag = nullptr;
+    if (int rc = b->tenv.err.get(b->stream, &flag)) return rc;
+    void* kernel = tenv_macro_kernel(b->W, mode);
     int& bpc = b->tenv.macro_bpc[mode];
-    if (!bpc)
-        if (int e = max_blocks_tenv_macro(b->W, mode, b->net->L.plane_off, &bpc))
-            return fail(PBN_E_HIP, "occupancy query: %s", hipGetErrorString((hipError_t)e));
+    if (int rc = cached_bpc(bpc, kernel, b->W, b->net->L.plane_off)) return rc;
     TenvMacroArgs a{};
-    a.state = b->d_state;
-    a.img = b->d_image;
-    a.L = b->net->L;
-    a.B = b->B;
-    a.env_base = b->env_base;
-    a.seed = b->seed;
+    fill_lane_env(b, a);
     a.update = b->update_count;
     a.actions = d_actions;
     a.limit = d_limit;
@@ -237,14 +194,13 @@ int pbn_tenv_macro_device(pbn_batch* b, const pbn_stateset* target, int mode, ui
     a.first_hit = d_first_hit;
     a.labels = d_labels;
     a.error = flag;
-    const int grid = b->grid_for(b->B, bpc);
-    if (int rc = timed_launch(b, "k_tenv_macro", [&] { return launch_tenv_macro(b->W, a, grid, b->stream); })) return rc;
+    if (int rc = launch_lane_env_step(b, "k_tenv_macro", kernel, a.L.plane_off, bpc, a)) return rc;
     // t_max, not the longest run of rounds (which the host does not know): the next call's draws stay disjoint from
     // this one's whatever the envs did, and whether or not an env was refused
     b->update_count += t_max;
     if (!check) return 0;
     int32_t err;
-    if (int rc = tenv_read_error_flag(b, flag, &err)) return rc;
+    if (int rc = b->tenv.err.read_and_clear(b, &err)) return rc;
     if (err)
         return fail(PBN_E_RANGE, "Invalid action: an action outside [0, %d] or a limit outside [1, %u] (envs holding "
                                  "one were left untouched)", b->N, mode == PBN_MACRO_INTERVAL ? (unsigned)t_max : 10u);
@@ -257,8 +213,19 @@ int pbn_tenv_reset_device(pbn_batch* b, const uint64_t* d_states, uint64_t n_sta
     if (int rc = check_table_batch(b, "pbn_tenv_reset_device")) return rc;
     if (n_states == 0 || n_states >> 32) return fail(PBN_E_INVALID, "n_states outside [1, 2^32)");
     SET_DEV(b);
-    TenvResetArgs a{b->d_state, b->B, b->env_base, b->seed, b->reset_count, d_states, (uint32_t)n_states, d_mask};
-    if (int rc = timed_launch(b, "k_tenv_reset", [&] { return launch_tenv_reset(b->W, a, b->stream); })) return rc;
+    // k_env_set_reset over one attractor (row_off null), n_steps left alone; n_states >= 1, so no env is skipped and
+    // the flag is never raised
+    EnvSetResetArgs a{};
+    a.state = b->d_state;
+    a.B = b->B;
+    a.env_base = b->env_base;
+    a.seed = b->seed;
+    a.reset_count = b->reset_count;
+    a.n_rows = (uint32_t)n_states;
+    a.rows = d_states;
+    a.mask = d_mask;
+    a.clear_node0 = 1;
+    if (int rc = timed_launch(b, "k_env_set_reset", [&] { return launch_env_set_reset(b->W, a, b->stream); })) return rc;
     b->reset_count++;
     return 0;
 }

@@ -129,6 +129,25 @@ struct PinBuf {
     }
 };
 
+struct pbn_batch;
+
+// A sticky device flag: kernels OR 1 into it for every env they skip whole, the host reads it when a caller asks
+// for a check. Zeroed at allocation and by every read. Each kernel family has its own, so that a family's check
+// reports that family's skips only.
+struct StickyFlag {
+    DevBuf buf;
+    int get(hipStream_t stream, int32_t** flag) {
+        if (!buf.p) {
+            if (int rc = buf.ensure(4)) return rc;
+            HIP_TRY(hipMemsetAsync(buf.p, 0, 4, stream));
+        }
+        *flag = (int32_t*)buf.p;
+        return 0;
+    }
+    // Waits for the batch's stream, reads the flag into *err and clears it (below pbn_batch).
+    inline int read_and_clear(pbn_batch* b, int32_t* err);
+};
+
 template <size_t N>
 inline void destroy_graph_execs(hipGraphExec_t (&x)[N]) {
     for (hipGraphExec_t& g : x) {
@@ -178,8 +197,9 @@ struct Knobs {
     int ssd_shared = -1;      // PBNSIM_SSD_SHARED: 0 = one wave per env, 4 / 8 = that many, 1 = the default
                               // count, -1 = by size
     bool mt_lane_walk = false;  // PBNSIM_MT_LANES=1: MT-mode steps of predictor-mix networks on k_mt_step
-    int envset_grid = 0;           // PBNSIM_ENVSET_GRID: cap on k_env_set's workgroups (tests: a small batch walks the
-                                   // grid-stride loop), 0 = by occupancy
+    int envset_grid = 0;           // PBNSIM_ENVSET_GRID: cap on the workgroups of every lane-per-env step launch (k_tenv_step,
+                                   // k_tenv_macro, k_env_set; tests: a small batch walks the grid-stride loop),
+                                   // 0 = by occupancy
     bool envset_no_hull = false;   // PBNSIM_ENVSET_NO_HULL=1 (measurement): k_env_set without the hull pre-filter
     bool envset_no_skip = false;   // PBNSIM_ENVSET_NO_SKIP=1 (measurement): k_env_set looks up after unchanged updates too
 };
@@ -200,7 +220,7 @@ struct pbn_batch {
     int roll_group = 1;  // lanes per env of the rollout kernel
     Knobs knob;
     PinBuf pin;                         // staging for small host<->device copies
-    DevBuf s_flip_err;                  // range-error flag of pbn_flip_device
+    StickyFlag s_flip_err;              // range-error flag of pbn_flip_device
     DevBuf s_act, s_obs, s_rew, s_flags, s_nup, s_replay_i, s_replay_k, s_off, s_mask;
 
     struct StepGraphs {
@@ -261,12 +281,12 @@ struct pbn_batch {
         uint64_t sync_steps = 0;   // synchronous-step counter (Philox)
     } aux;
     struct Tenv {        // the PBN-v0 env on the device (pbn_abi_tenv.cpp)
-        DevBuf err;      // sticky range flag of pbn_tenv_step_device, zeroed at allocation and after every check
+        StickyFlag err;  // of pbn_tenv_step_device / _macro_device, read by their checked calls
         int bpc = 0;     // k_tenv_step's resident workgroups per CU (0: not asked yet)
         int macro_bpc[2] = {0, 0};  // k_tenv_macro's, by mode
     } tenv;
     struct EnvSet {      // the until-attractor env over a state set (pbn_abi_env_set.cpp)
-        DevBuf err;      // sticky flag of pbn_env_set_step_device / _reset_device, read and cleared by pbn_env_set_check
+        StickyFlag err;  // of pbn_env_set_step_device / _reset_device, read by pbn_env_set_check
         int bpc = 0;     // k_env_set's resident workgroups per CU (0: not asked yet)
     } envset;
     // timing: mode 1 = an event pair around every launch; mode 2 = one region
@@ -352,6 +372,63 @@ struct pbn_stateset {
     DevBuf meta, keys;  // given back by the destructor (pbn_stateset_destroy makes the device current)
     SetView view() const { return SetView{(const uint32_t*)meta.p, (const uint64_t*)keys.p, t.slots}; }
 };
+
+inline int StickyFlag::read_and_clear(pbn_batch* b, int32_t* err) {
+    int32_t* flag = nullptr;
+    if (int rc = get(b->stream, &flag)) return rc;
+    if (!b->pin.ready()) return fail(PBN_E_NOMEM, "pinned staging buffer");
+    HIP_TRY(hipMemcpyAsync(b->pin.p, flag, 4, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipMemsetAsync(flag, 0, 4, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    memcpy(err, b->pin.p, 4);
+    return 0;
+}
+
+// ---- what the entry points of the lane-per-env kernels share (pbn_abi_tenv.cpp, pbn_abi_env_set.cpp)
+
+// The set can serve this batch's launches: uploaded, on the batch's device, over states of the batch's width.
+// The two families answer a host-only set with different codes (pbn_tenv_*: PBN_E_STATE, pbn_env_set_*:
+// PBN_E_INVALID), which their callers match; host_only_code keeps each its own.
+inline int check_set_for_batch(const pbn_batch* b, const pbn_stateset* s, const char* what, int host_only_code) {
+    if (s->device < 0) return fail(host_only_code, "%s is a host-only state set (created with device -1)", what);
+    if (s->device != b->device)
+        return fail(PBN_E_INVALID, "%s lives on device %d, the batch on device %d", what, s->device, b->device);
+    if (s->t.n_nodes != b->N)
+        return fail(PBN_E_INVALID, "%s holds states of %d nodes, the batch has %d", what, s->t.n_nodes, b->N);
+    return 0;
+}
+
+inline int check_two_nodes(const pbn_batch* b) {
+    if (b->N < 2) return fail(PBN_E_UNSUPPORTED, "PBN.step updates a node in [1, N-1]: the network needs two nodes");
+    return 0;
+}
+
+// The kernel's resident workgroups per CU, asked once per batch: slot 0 = not asked yet.
+inline int cached_bpc(int& slot, void* kernel, int W, uint32_t plane_off) {
+    if (!slot)
+        if (int e = max_blocks_lane_env(kernel, W, plane_off, &slot))
+            return fail(PBN_E_HIP, "occupancy query: %s", hipGetErrorString((hipError_t)e));
+    return 0;
+}
+
+// The fields every lane-per-env argument struct starts from.
+template <class Args>
+inline void fill_lane_env(const pbn_batch* b, Args& a) {
+    a.state = b->d_state;
+    a.img = b->d_image;
+    a.L = b->net->L;
+    a.B = b->B;
+    a.env_base = b->env_base;
+    a.seed = b->seed;
+}
+
+// One step launch over the whole batch: the grid is what is resident, capped by PBNSIM_ENVSET_GRID.
+template <class Args>
+inline int launch_lane_env_step(pbn_batch* b, const char* name, void* kernel, uint32_t plane_off, int bpc, Args& a) {
+    int grid = b->grid_for(b->B, bpc);
+    if (b->knob.envset_grid > 0) grid = std::min(grid, b->knob.envset_grid);
+    return timed_launch(b, name, [&] { return launch_lane_env(kernel, b->W, plane_off, grid, b->stream, &a); });
+}
 
 // Attractor discovery (pbn_reach.hip); entry points in pbn_abi_reach.cpp.
 struct pbn_reach {

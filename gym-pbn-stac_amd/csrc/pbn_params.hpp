@@ -350,7 +350,7 @@ struct ReachArgs {
 };
 
 // The PBN-v0 env on the device (pbn_tenv.hip): an exact state set a kernel can query
-// (pbn_stateset.hpp), the fused step and the reset over a table of states.
+// (pbn_stateset.hpp) and the fused step; its reset over a table of states is EnvSetResetArgs' (below).
 struct SetView {
     const uint32_t* meta;  // [slots] 0 = empty, else label + 1
     const uint64_t* keys;  // [slots][W]
@@ -410,15 +410,6 @@ struct TenvMacroArgs {
     int32_t* error;            // the sticky flag of TenvArgs::error
 };
 
-struct TenvResetArgs {
-    uint64_t* state;
-    uint64_t B, env_base, seed;
-    uint32_t reset_count;
-    const uint64_t* states;  // [n_states][W]
-    uint32_t n_states;       // >= 1
-    const uint8_t* mask;     // [B] or null
-};
-
 // The until-attractor multi-flip env over an exact labelled state set (k_env_set, pbn_env_set.hip):
 // k_env's env step with "attracting" read as "member of the set", a target label per env.
 struct EnvSetArgs {
@@ -444,13 +435,15 @@ struct EnvSetArgs {
     int32_t* error;          // sticky: set to 1 by an env whose action row names no node (the env is skipped)
 };
 
+// k_env_set_reset serves pbn_env_set_reset_device and, with row_off and n_steps null, pbn_tenv_reset_device.
 struct EnvSetResetArgs {
     uint64_t* state;
-    int64_t* n_steps;
+    int64_t* n_steps;          // zeroed for reset envs, if non-null
     uint64_t B, env_base, seed;
     uint32_t reset_count;
+    uint32_t n_rows;           // row_off null: rows is one attractor of n_rows >= 1 rows
     const uint64_t* rows;      // [S][W], ordered by label
-    const uint32_t* row_off;   // [n_labels + 1]: attractor k's rows are row_off[k] .. row_off[k + 1] - 1
+    const uint32_t* row_off;   // [n_labels + 1]: attractor k's rows are row_off[k] .. row_off[k + 1] - 1; or null
     int32_t n_labels;
     int32_t source_label;      // the source of every env when source_labels is null
     const int32_t* source_labels;  // [B] or null
@@ -461,17 +454,18 @@ struct EnvSetResetArgs {
 
 // Launchers (pbn_step.hip, pbn_state.hip, pbn_env.hip, pbn_group.hip, pbn_mt.hip, pbn_ssd.hip, pbn_sync.hip, pbn_reach.hip,
 // pbn_tenv.hip, pbn_tenv_macro.hip, pbn_env_set.hip). Return hipError_t as int.
-int launch_env_set(int W, const EnvSetArgs& a, int grid, void* stream);
+// The lane-per-env kernels (pbn_lane_env.hpp): each file picks its kernel (nullptr: none for that shape), one
+// launcher and one occupancy query serve them all. plane_off: the LDS byte offset of the kernel's state planes;
+// args: the kernel's argument struct.
+void* tenv_step_kernel(int W);
+void* tenv_macro_kernel(int W, int mode);
+void* env_set_kernel(int W, int kind);
+int launch_lane_env(void* kernel, int W, uint32_t plane_off, int grid, void* stream, void* args);
+int max_blocks_lane_env(void* kernel, int W, uint32_t plane_off, int* blocks_per_cu);
 int launch_env_set_reset(int W, const EnvSetResetArgs& a, void* stream);
-int max_blocks_env_set(int W, int kind, uint32_t image_bytes, int* blocks_per_cu);
 enum { REACH_K_UNSTABLE = 0, REACH_K_SEED, REACH_K_EXPAND, REACH_K_BACK_START, REACH_K_BACK, REACH_K_HULL };
 int launch_reach(int W, int which, const ReachArgs& a, int grid, void* stream);
 int launch_set_lookup(int W, const SetLookupArgs& a, void* stream);
-int launch_tenv_step(int W, const TenvArgs& a, int grid, void* stream);
-int launch_tenv_reset(int W, const TenvResetArgs& a, void* stream);
-int max_blocks_tenv(int W, uint32_t image_bytes, int* blocks_per_cu);
-int launch_tenv_macro(int W, const TenvMacroArgs& a, int grid, void* stream);
-int max_blocks_tenv_macro(int W, int mode, uint32_t image_bytes, int* blocks_per_cu);
 int launch_bump(uint64_t* p, uint64_t k, void* stream);
 int launch_set_counters(uint64_t* p, uint64_t v, uint32_t n, void* stream);
 int launch_step(int W, const StepArgs& a, int store_mode, int replay, int sb, int grid, void* stream);

@@ -26,7 +26,75 @@ from .batch import EnvConfig, Net, PBNBatch
 from .network import PredictorNetwork, load_network
 
 
-class TorchVecPBNTargetMultiEnv:
+class _TorchVecBase:
+    """What the device-resident envs share: a :class:`PBNBatch` on torch's current stream, the conversions between
+    torch tensors and what the launches read and write, and ``close``. A subclass sets ``batch``, ``device``,
+    ``num_envs``, ``N``, ``W`` and lists the state sets it owns in ``_sets``."""
+
+    _sets = ()
+
+    def _use_stream(self):
+        import torch
+
+        self.batch.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _bits(self, words=None):
+        """[B][N] uint8 node values (k_unpack) from packed words [B][W] (None = the live state)."""
+        import torch
+
+        out = torch.empty((self.num_envs, self.N), dtype=torch.uint8, device=self.device)
+        self.batch.unpack_bits_device(out.data_ptr(), 0 if words is None else words.data_ptr())
+        return out
+
+    def observation_words(self):
+        """The live state as packed words ``[B][W]`` int64: a fresh device tensor per call."""
+        import torch
+
+        self._use_stream()
+        words = torch.empty((self.num_envs, self.W), dtype=torch.int64, device=self.device)
+        self.batch.get_state_device(words.data_ptr())
+        return words
+
+    def _mask(self, mask):
+        """A reset mask (None: every env) as the uint8 tensor a launch reads, or None."""
+        import torch
+
+        if mask is None:
+            return None
+        # same stream as the kernel: the allocator cannot hand the copy's memory out before it ran
+        return mask.to(device=self.device, dtype=torch.uint8).contiguous()
+
+    def _actions(self, actions, two_d: bool):
+        """``actions`` as a contiguous int32 device tensor with one row per env: ``[B][A]`` (``two_d``; ``[B]`` is
+        taken as ``A = 1``) or ``[B]``."""
+        import torch
+
+        a = actions
+        if two_d and a.dim() == 1:
+            a = a.unsqueeze(1)
+        a = a.to(device=self.device, dtype=torch.int32).contiguous()
+        if not two_d:
+            a = a.reshape(-1)
+        if a.shape[0] != self.num_envs:
+            raise ValueError(f"actions for {a.shape[0]} envs, the batch has {self.num_envs}")
+        return a
+
+    @staticmethod
+    def _decode_flags(flags):
+        """The flag bytes a step launch wrote -> ``(terminated, truncated, capped)`` bool tensors."""
+        return (flags & L.FLAG_TERMINATED) != 0, (flags & L.FLAG_TRUNCATED) != 0, (flags & L.FLAG_CAPPED) != 0
+
+    def close(self):
+        import torch
+
+        torch.cuda.current_stream(self.device).synchronize()
+        self.batch.set_stream(None)
+        self.batch.close()
+        for s in self._sets:
+            s.close()
+
+
+class TorchVecPBNTargetMultiEnv(_TorchVecBase):
     def __init__(self, network, attractors, n_envs: int, horizon: int = 100, device: int = 0, seed: int = 0,
                  env_id_base: int = 0, update_cap: int = 1 << 20, auto_reset: bool = False):
         import torch
@@ -45,42 +113,17 @@ class TorchVecPBNTargetMultiEnv:
         self.action_space = spaces.MultiDiscrete(self.N + 1)
         B = self.num_envs
         with torch.cuda.device(self.device):
-            self._words = torch.empty((B, self.W), dtype=torch.int64, device=self.device)
             self._reward = torch.empty(B, dtype=torch.int32, device=self.device)
             self._flags = torch.empty(B, dtype=torch.uint8, device=self.device)
             self._nup = torch.empty(B, dtype=torch.int32, device=self.device)
         self._use_stream()
 
-    def _use_stream(self):
-        import torch
-
-        self.batch.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _bits(self, words=None):
-        """[B][N] uint8 node values (k_unpack) from packed words [B][W] (None = the live state)."""
-        import torch
-
-        out = torch.empty((self.num_envs, self.N), dtype=torch.uint8, device=self.device)
-        self.batch.unpack_bits_device(out.data_ptr(), 0 if words is None else words.data_ptr())
-        return out
-
-    def observation_words(self):
-        self._use_stream()
-        self.batch.get_state_device(self._words.data_ptr())
-        return self._words
-
     def reset(self, mask=None):
         """Reset every env (``mask`` None) or the envs where the device bool/uint8 ``mask`` is set
         (``reset``, :227-259, Philox draws); returns observations [B][N] uint8 on the device."""
-        import torch
-
         self._use_stream()
-        if mask is None:
-            self.batch.env_reset_device(self.cfg, 0)
-        else:
-            # same stream as the kernel: the allocator cannot hand m's memory out before it ran
-            m = mask.to(device=self.device, dtype=torch.uint8).contiguous()
-            self.batch.env_reset_device(self.cfg, m.data_ptr())
+        m = self._mask(mask)
+        self.batch.env_reset_device(self.cfg, 0 if m is None else m.data_ptr())
         return self._bits()
 
     def step(self, actions):
@@ -89,34 +132,20 @@ class TorchVecPBNTargetMultiEnv:
         info)`` as device tensors; ``info`` holds ``n_updates``, ``capped`` and ``obs_words``."""
         import torch
 
-        a = actions
-        if a.dim() == 1:
-            a = a.unsqueeze(1)
-        a = a.to(device=self.device, dtype=torch.int32).contiguous()
-        if a.shape[0] != self.num_envs:
-            raise ValueError(f"actions for {a.shape[0]} envs, the batch has {self.num_envs}")
+        a = self._actions(actions, two_d=True)
         self._use_stream()
         words = torch.empty((self.num_envs, self.W), dtype=torch.int64, device=self.device)
         self.batch.env_step_multi_device(self.cfg, a.data_ptr(), a.shape[1], words.data_ptr(),
                                          self._reward.data_ptr(), self._flags.data_ptr(), self._nup.data_ptr(),
                                          offset=1, dedup=True, update_cap=self.update_cap)
-        flags = self._flags
-        term = (flags & L.FLAG_TERMINATED) != 0
-        trunc = (flags & L.FLAG_TRUNCATED) != 0
-        info = {"n_updates": self._nup.clone(), "capped": (flags & L.FLAG_CAPPED) != 0, "obs_words": words}
+        term, trunc, capped = self._decode_flags(self._flags)
+        info = {"n_updates": self._nup.clone(), "capped": capped, "obs_words": words}
         obs = self._bits(words)
         reward = self._reward.clone()
         if self.auto_reset:
             done = (term | trunc).to(torch.uint8).contiguous()
             self.batch.env_reset_device(self.cfg, done.data_ptr())
         return obs, reward, term, trunc, info
-
-    def close(self):
-        import torch
-
-        torch.cuda.current_stream(self.device).synchronize()
-        self.batch.set_stream(None)
-        self.batch.close()
 
 
 def _packed_attractors(network, net, all_attractors, device: int, seed: int):
@@ -160,7 +189,7 @@ def _packed_attractors(network, net, all_attractors, device: int, seed: int):
     return out
 
 
-class TorchVecPBNEnv:
+class TorchVecPBNEnv(_TorchVecBase):
     """B copies of the ``PBN-v0`` MDP (``pbn_env.py:125-188``) resident on the device: the twin of
     :class:`gym_pbn_amd.envs.VecPBNEnv` for agents on the GPU.
 
@@ -217,6 +246,7 @@ class TorchVecPBNEnv:
         target = np.unique(np.concatenate(parts), axis=0)
         self.target_words = target
         self.target = StateSet(target, self.N, device=device)
+        self._sets = (self.target,)
         attracting = np.unique(np.concatenate(self.attractors), axis=0)
         self.n_attracting = int(attracting.shape[0])
         self.batch = PBNBatch(self.net, self.num_envs, device=device, env_id_base=env_id_base, seed=seed)
@@ -230,11 +260,6 @@ class TorchVecPBNEnv:
             self._flags = torch.empty(B, dtype=torch.uint8, device=self.device)
         self._use_stream()
 
-    def _use_stream(self):
-        import torch
-
-        self.batch.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
-
     def info(self) -> dict:
         """The target set's ``pbn_stateset_info`` (``n_states``, ``table_slots``, ``max_probe``, ...) and
         ``n_attracting``, the number of attracting states reset draws from."""
@@ -242,34 +267,28 @@ class TorchVecPBNEnv:
         d["n_attracting"] = self.n_attracting
         return d
 
-    def _bits(self, words=None):
-        import torch
-
-        out = torch.empty((self.num_envs, self.N), dtype=torch.uint8, device=self.device)
-        self.batch.unpack_bits_device(out.data_ptr(), 0 if words is None else words.data_ptr())
-        return out
-
-    def observation_words(self):
-        import torch
-
-        self._use_stream()
-        words = torch.empty((self.num_envs, self.W), dtype=torch.int64, device=self.device)
-        self.batch.get_state_device(words.data_ptr())
-        return words
-
     def reset(self, mask=None):
         """Every env (``mask`` None) or the envs where the device bool / uint8 ``mask`` is set take a state drawn
         uniformly from the attracting set, node 0 cleared (``PBN.reset``, ``pbn.py:118``); returns observations
         ``[B][N]`` uint8 on the device."""
+        self._use_stream()
+        self._reset(self._mask(mask))
+        return self._bits()
+
+    def _reset(self, m):
+        self.batch.tenv_reset_device(self._attracting.data_ptr(), self.n_attracting, 0 if m is None else m.data_ptr())
+
+    def _finish(self, words):
+        """A step's tail once its launch wrote ``words`` and the flags: ``(obs, terminated, truncated)``, then the
+        auto-reset of the envs that ended (``PBN-v0`` and the macro envs never truncate)."""
         import torch
 
-        self._use_stream()
-        if mask is None:
-            self.batch.tenv_reset_device(self._attracting.data_ptr(), self.n_attracting, 0)
-        else:
-            m = mask.to(device=self.device, dtype=torch.uint8).contiguous()
-            self.batch.tenv_reset_device(self._attracting.data_ptr(), self.n_attracting, m.data_ptr())
-        return self._bits()
+        term = self._decode_flags(self._flags)[0]
+        trunc = torch.zeros(self.num_envs, dtype=torch.bool, device=self.device)
+        obs = self._bits(words)
+        if self.auto_reset:
+            self._reset(term.to(torch.uint8).contiguous())
+        return obs, term, trunc
 
     def step(self, actions, check: bool = False):
         """``actions``: int tensor ``[B]`` on the GPU, values in ``[0, N-1]``. An env given any other value is left
@@ -277,9 +296,7 @@ class TorchVecPBNEnv:
         default stays asynchronous, and a later checked call reports)."""
         import torch
 
-        a = actions.to(device=self.device, dtype=torch.int32).contiguous().reshape(-1)
-        if a.shape[0] != self.num_envs:
-            raise ValueError(f"actions for {a.shape[0]} envs, the batch has {self.num_envs}")
+        a = self._actions(actions, two_d=False)
         self._use_stream()
         B = self.num_envs
         words = torch.empty((B, self.W), dtype=torch.int64, device=self.device)
@@ -289,21 +306,8 @@ class TorchVecPBNEnv:
                                     d_obs=words.data_ptr(), d_labels=label.data_ptr(),
                                     reward_target=self.REWARD_TARGET, step_cost=self.STEP_COST,
                                     action_cost=self.ACTION_COST, check=check)
-        term = (self._flags & L.FLAG_TERMINATED) != 0
-        trunc = torch.zeros(B, dtype=torch.bool, device=self.device)
-        obs = self._bits(words)
-        if self.auto_reset:
-            done = term.to(torch.uint8).contiguous()
-            self.batch.tenv_reset_device(self._attracting.data_ptr(), self.n_attracting, done.data_ptr())
+        obs, term, trunc = self._finish(words)
         return obs, reward, term, trunc, {"obs_words": words, "label": label}
-
-    def close(self):
-        import torch
-
-        torch.cuda.current_stream(self.device).synchronize()
-        self.batch.set_stream(None)
-        self.batch.close()
-        self.target.close()
 
 
 def labelled_attractors(network, attractors, net=None, device: int = 0, seed: int = 0):
@@ -341,7 +345,7 @@ def labelled_attractors(network, attractors, net=None, device: int = 0, seed: in
     return rows, labels, row_off
 
 
-class TorchVecPBNTargetMultiSetEnv:
+class TorchVecPBNTargetMultiSetEnv(_TorchVecBase):
     """:class:`TorchVecPBNTargetMultiEnv` over attractors given as exact state lists: one labelled
     :class:`~gym_pbn_amd.stateset.StateSet` (label = the attractor's index) takes the place of the cubes, so an
     attractor may have any shape and up to ``2**24`` states in all, ``info["label"]`` says which attractor each env
@@ -378,6 +382,7 @@ class TorchVecPBNTargetMultiSetEnv:
         self.n_attractors = len(row_off) - 1
         self.row_off = row_off
         self.set = StateSet(rows, self.N, labels=labels, device=device)
+        self._sets = (self.set,)
         self.horizon, self.update_cap = int(horizon), int(update_cap)
         self.reward_success, self.action_cost = int(reward_success), int(action_cost)
         self.auto_reset = bool(auto_reset)
@@ -393,17 +398,6 @@ class TorchVecPBNTargetMultiSetEnv:
             self.target = torch.full((B,), self.n_attractors - 1, dtype=torch.int32, device=self.device)
             self._flags = torch.empty(B, dtype=torch.uint8, device=self.device)
         self._use_stream()
-
-    _use_stream = TorchVecPBNTargetMultiEnv._use_stream
-    _bits = TorchVecPBNTargetMultiEnv._bits
-
-    def observation_words(self):
-        import torch
-
-        self._use_stream()
-        words = torch.empty((self.num_envs, self.W), dtype=torch.int64, device=self.device)
-        self.batch.get_state_device(words.data_ptr())
-        return words
 
     def _assign(self, held, value, m):
         """``held[e] = value[e]`` (an int or a device int tensor ``[B]``) for the envs of mask ``m`` (None: all)."""
@@ -435,10 +429,8 @@ class TorchVecPBNTargetMultiSetEnv:
         tensor ``[B]`` of attractor indices, stored for the envs being reset and kept until their next reset that
         names one. An env whose source is no attractor is left as it is (``batch.env_set_check()`` reports it).
         Returns observations ``[B][N]`` uint8 on the device."""
-        import torch
-
         self._use_stream()
-        m = None if mask is None else mask.to(device=self.device, dtype=torch.uint8).contiguous()
+        m = self._mask(mask)
         self._assign(self.source, source, m)
         self._assign(self.target, target, m)
         self._reset(m)
@@ -451,12 +443,7 @@ class TorchVecPBNTargetMultiSetEnv:
         capped); ``terminated`` is ``label == target`` of the env."""
         import torch
 
-        a = actions
-        if a.dim() == 1:
-            a = a.unsqueeze(1)
-        a = a.to(device=self.device, dtype=torch.int32).contiguous()
-        if a.shape[0] != self.num_envs:
-            raise ValueError(f"actions for {a.shape[0]} envs, the batch has {self.num_envs}")
+        a = self._actions(actions, two_d=True)
         self._use_stream()
         B = self.num_envs
         words = torch.empty((B, self.W), dtype=torch.int64, device=self.device)
@@ -468,22 +455,12 @@ class TorchVecPBNTargetMultiSetEnv:
                                        d_target_labels=self.target.data_ptr(), offset=1, dedup=True,
                                        update_cap=self.update_cap, horizon=self.horizon,
                                        reward_success=self.reward_success, action_cost=self.action_cost)
-        flags = self._flags
-        term = (flags & L.FLAG_TERMINATED) != 0
-        trunc = (flags & L.FLAG_TRUNCATED) != 0
-        info = {"n_updates": nup, "capped": (flags & L.FLAG_CAPPED) != 0, "obs_words": words, "label": label}
+        term, trunc, capped = self._decode_flags(self._flags)
+        info = {"n_updates": nup, "capped": capped, "obs_words": words, "label": label}
         obs = self._bits(words)
         if self.auto_reset:
             self._reset((term | trunc).to(torch.uint8).contiguous())
         return obs, reward, term, trunc, info
-
-    def close(self):
-        import torch
-
-        torch.cuda.current_stream(self.device).synchronize()
-        self.batch.set_stream(None)
-        self.batch.close()
-        self.set.close()
 
 
 __all__ = ["TorchVecPBNTargetMultiEnv", "TorchVecPBNEnv", "TorchVecPBNTargetMultiSetEnv", "labelled_attractors"]

@@ -22,7 +22,7 @@ from __future__ import annotations
 from . import spaces
 from .macro_env import (MACRO_INTERVAL, MACRO_TRIGGER, N_PROBS, TENV_MACRO_MAX_T, decode_discrete, gamma_powers,
                         stop_thresholds)
-from .torch_env import L, TorchVecPBNEnv
+from .torch_env import TorchVecPBNEnv
 
 
 class _TorchVecMacroEnv(TorchVecPBNEnv):
@@ -76,12 +76,7 @@ class _TorchVecMacroEnv(TorchVecPBNEnv):
                                      d_first_hit=first_hit.data_ptr(), d_labels=label.data_ptr(),
                                      reward_target=self.REWARD_TARGET, step_cost=self.STEP_COST,
                                      action_cost=self.ACTION_COST, check=check, **kw)
-        term = (self._flags & L.FLAG_TERMINATED) != 0
-        trunc = torch.zeros(B, dtype=torch.bool, device=self.device)
-        obs = self._bits(words)
-        if self.auto_reset:
-            done = term.to(torch.uint8).contiguous()
-            self.batch.tenv_reset_device(self._attracting.data_ptr(), self.n_attracting, done.data_ptr())
+        obs, term, trunc = self._finish(words)
         return obs, reward, term, trunc, {"obs_words": words, "label": label, "interval": interval,
                                           "first_hit": first_hit}
 

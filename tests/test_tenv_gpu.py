@@ -1,4 +1,4 @@
-"""The ``PBN-v0`` env on the device: the fused step (k_tenv_step), the reset over a table of states (k_tenv_reset)
+"""The ``PBN-v0`` env on the device: the fused step (k_tenv_step), the reset over a table of states (k_env_set_reset)
 and ``TorchVecPBNEnv`` on top of them. Every comparison is bit-exact.
 
 The fused step is held against the calls it replaces (``PBNBatch.flip`` + ``step(1)`` + host ``StateSet.lookup``)
@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from shape_cases import tt_net
 
 pytestmark = pytest.mark.gpu
 
@@ -129,6 +130,59 @@ def test_fused_step_equals_flip_step_lookup(name, B, base, oracle_mod):
         seen_term |= bool(term.any())
         seen_not |= bool((~term).any())
     assert seen_term and seen_not
+    f.close()
+    target.close()
+
+
+@pytest.mark.parametrize("name", ["tt6", 65])
+def test_one_workgroup_walks_every_env(name, monkeypatch, oracle_mod):
+    """B = 600 with the grid capped at one workgroup (PBNSIM_ENVSET_GRID=1): every lane takes two or three envs in
+    the grid-stride loop, and on the third trip only 88 lanes are live -- one full wave, one partly live, two that
+    have left. tt6: W = 1; ttk3_65: W = 2, node 64 alone in the second word. Expected values: the oracle's update of
+    the flipped state and the host lookup. Env 520 (third trip) holds an invalid action in step 1: skipped whole."""
+    from gym_pbn_amd.batch import Net, PBNBatch
+    from gym_pbn_amd.stateset import StateSet
+
+    network = tt_net(name) if isinstance(name, int) else _network(name)
+    net = Net(network)
+    N, W, B, seed, base, steps = net.n_nodes, net.n_words, 600, 11, 3, 3
+    orc = oracle_mod.Oracle(network)
+    rng = np.random.default_rng(N)
+    acts = _actions(rng, B, N, steps)
+    acts[0, :3], acts[2, -1] = [1, N - 1, 0], N - 1  # node N - 1 on the first trip and on the last live lane
+    acts[1, 520] = N
+    monkeypatch.setenv("PBNSIM_ENVSET_GRID", "1")
+    f = PBNBatch(net, B, env_id_base=base, seed=seed)
+    f.randomize()
+    prev = f.get_state()
+    want = []
+    for t in range(steps):
+        ok = np.where(acts[t] < N, acts[t], 0)
+        now = orc.step_philox(_flip_rows(prev, ok), seed, base, t, 1)
+        now[acts[t] >= N] = prev[acts[t] >= N]
+        want.append(now)
+        prev = now
+    pool = np.unique(np.concatenate(want), axis=0)
+    members = pool[rng.random(len(pool)) < 0.5]
+    target = StateSet(members, N, labels=np.arange(len(members)) % 5, device=0)
+    out = _Out(B, W)
+    for t in range(steps):
+        out.obs.fill_(SENTINEL)
+        out.reward.fill_(SENTINEL)
+        obs, reward, flags, label = out.step(f, target, acts[t])
+        bad = acts[t] >= N
+        assert bad.sum() == (t == 1)
+        assert np.array_equal(f.get_state(), want[t]), t
+        assert np.array_equal(obs[~bad], want[t][~bad]), t
+        lab = target.lookup(want[t])
+        term = lab >= 0
+        assert term[512:].any() and (~term[512:]).any() and term[:256].any()
+        assert np.array_equal(label[~bad], lab[~bad]), t
+        assert np.array_equal(flags[~bad], term[~bad].astype(np.uint8)), t
+        assert np.array_equal(reward[~bad], np.where(term, 20, -4 - (acts[t] != 0)).astype(np.int32)[~bad]), t
+        assert (obs[bad].view(np.int64) == SENTINEL).all() and (reward[bad] == SENTINEL).all()
+    with pytest.raises(ValueError, match="Invalid action"):
+        out.step(f, target, np.zeros(B, np.int32), check=True)  # env 520's skip, noted on the third trip
     f.close()
     target.close()
 

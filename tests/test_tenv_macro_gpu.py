@@ -318,6 +318,57 @@ def test_an_invalid_env_is_skipped_whole_and_reported_once(name, mode):
     target.close()
 
 
+@pytest.mark.parametrize("mode", [INTERVAL, TRIGGER])
+@pytest.mark.parametrize("name", ["tt6", 65])
+def test_one_workgroup_walks_every_env(name, mode, monkeypatch):
+    """B = 600 with the grid capped at one workgroup (PBNSIM_ENVSET_GRID=1): every lane takes two or three envs in
+    the grid-stride loop, and on the third trip only 88 lanes are live -- one full wave, one partly live, two that
+    have left. The limits are ragged, so the lanes of a wave stop at different rounds on every trip. tt6: W = 1;
+    ttk3_65: W = 2. Env 515 (third trip) holds an invalid limit: skipped whole and reported."""
+    from gym_pbn_amd.batch import PBNBatch
+    from gym_pbn_amd.stateset import StateSet
+
+    net = _net(name)
+    N, W, B, base, bad_env = net.n_nodes, net.n_words, 600, 2, 515
+    rng = np.random.default_rng(N + mode)
+    monkeypatch.setenv("PBNSIM_ENVSET_GRID", "1")
+    b = PBNBatch(net, B, env_id_base=base, seed=SEED)
+    b.randomize()
+    s0 = b.get_state()
+    b.close()
+    gpow, thr = _tables(T_MAX)
+    lim_max = T_MAX if mode == INTERVAL else 10
+    acts = _actions(rng, B, N)
+    acts[-1] = N  # node N - 1 on the last live lane of the third trip
+    lims = rng.integers(1, lim_max + 1, size=B).astype(np.int32)
+    lims[bad_env] = 0
+    bad = np.arange(B) == bad_env
+    ok_acts = np.where(bad, 0, acts).astype(np.int32)
+    ok_lims = np.where(bad, 1, lims)
+    rec = _records(net, B, base, SEED, s0, U0, ok_acts, T_MAX)
+    pool = np.unique(rec.reshape(-1, W), axis=0)
+    target = StateSet(pool[rng.random(len(pool)) < 0.5], N, device=0)
+    labels = np.stack([target.lookup(r) for r in rec])
+    rounds = ok_lims if mode == INTERVAL else _stop_rounds(SEED, base, U0, ok_lims, T_MAX, thr)[0]
+    for trip in (slice(0, 256), slice(256, 512), slice(512, 600)):
+        assert len(set(rounds[trip][:64].tolist())) > 1, "the first wave of a trip is not ragged"
+        assert _both_branches(labels[:, trip], rounds[trip])
+    want = _expect(rec, labels, ok_acts, rounds, mode, gpow)
+    f = _fresh(net, B, base, s0)
+    out = _Out(B, W)
+    got = out.step(f, target, mode, T_MAX, acts, lims)
+    state = f.get_state()
+    assert np.array_equal(state[bad], s0[bad])
+    _assert_equal(got, want, state, rows=~bad)
+    assert (got["obs"][bad].view(np.int64) == SENTINEL).all() and (got["reward"][bad] == SENTINEL).all()
+    assert (got["flags"][bad] == 99).all() and (got["interval"][bad] == SENTINEL).all()
+    assert f.counters()["update_count"] == U0 + T_MAX
+    with pytest.raises(ValueError, match="Invalid action"):
+        out.step(f, target, mode, T_MAX, np.zeros(B, np.int32), np.ones(B, np.int32), check=True)
+    f.close()
+    target.close()
+
+
 @pytest.mark.parametrize("N", SHAPES)
 def test_every_state_width(N):
     """One interval-mode call per words-per-env instantiation, with flips on both sides of the word boundaries and
