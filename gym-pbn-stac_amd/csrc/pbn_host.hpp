@@ -198,7 +198,7 @@ struct Knobs {
                               // count, -1 = by size
     bool mt_lane_walk = false;  // PBNSIM_MT_LANES=1: MT-mode steps of predictor-mix networks on k_mt_step
     int envset_grid = 0;           // PBNSIM_ENVSET_GRID: cap on the workgroups of every lane-per-env step launch (k_tenv_step,
-                                   // k_tenv_macro, k_env_set; tests: a small batch walks the grid-stride loop),
+                                   // k_tenv_macro, k_env_set, k_census; tests: a small batch walks the grid-stride loop),
                                    // 0 = by occupancy
     bool envset_no_hull = false;   // PBNSIM_ENVSET_NO_HULL=1 (measurement): k_env_set without the hull pre-filter
     bool envset_no_skip = false;   // PBNSIM_ENVSET_NO_SKIP=1 (measurement): k_env_set looks up after unchanged updates too

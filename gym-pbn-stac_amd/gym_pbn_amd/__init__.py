@@ -39,6 +39,10 @@ def __getattr__(name):
         from .stateset import StateSet
 
         return StateSet
+    if name in ("StateCensus", "CensusResult", "statistical_attractors"):
+        from . import census
+
+        return getattr(census, name)
     if name in ("TorchVecPBNEnv", "TorchVecPBNTargetMultiEnv", "TorchVecPBNTargetMultiSetEnv"):
         from . import torch_env
 

@@ -107,6 +107,18 @@ class StateSetInfo(C.Structure):
 
 STATESET_MAX_STATES = 1 << 24
 
+
+class CensusInfo(C.Structure):
+    _fields_ = [
+        ("n_nodes", C.c_int32), ("n_words", C.c_int32), ("device", C.c_int32),
+        ("max_states", C.c_uint64), ("table_slots", C.c_uint64), ("n_states", C.c_uint64),
+        ("visits", C.c_uint64), ("dropped", C.c_uint64),
+    ]
+
+
+CENSUS_MAX_STATES = 1 << 24     # PBN_CENSUS_MAX_STATES
+CENSUS_MAX_UPDATES = 65536      # PBN_CENSUS_MAX_UPDATES: updates per pbn_census_run_device call
+
 # pbn_tenv_macro_device: modes (PBN_MACRO_*) and the cap on t_max (PBN_TENV_MACRO_MAX_T)
 from .macro_env import MACRO_INTERVAL, MACRO_TRIGGER, TENV_MACRO_MAX_T  # noqa: E402,F401
 
@@ -189,6 +201,13 @@ SIGNATURES = {
                                           C.c_int32, C.c_int, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pbn_env_set_reset_device": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, _vp, _vp]),
     "pbn_env_set_check": (C.c_int, [_vp]),
+    "pbn_census_create": (C.c_int, [C.c_int32, C.c_int, C.c_uint64, _PP]),
+    "pbn_census_destroy": (None, [_vp]),
+    "pbn_census_clear": (C.c_int, [_vp]),
+    "pbn_census_get_info": (C.c_int, [_vp, C.POINTER(CensusInfo)]),
+    "pbn_census_run_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _u64p]),
+    "pbn_census_read": (C.c_int, [_vp, _u64p, _u64p, C.c_uint64, _u64p]),
+    "pbn_census_get_stats": (C.c_int, [_vp, _u64p, _u64p]),
 }
 
 

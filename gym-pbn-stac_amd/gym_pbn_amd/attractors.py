@@ -265,6 +265,17 @@ class AttractorResult:
             if self.attractors else np.zeros(0, np.int32)
         return StateSet(rows, self.n_nodes, labels=labels, device=device)
 
+    def occupancy(self, census_result):
+        """Where the mass of a :class:`gym_pbn_amd.census.CensusResult` goes: ``(per_attractor, outside)`` --
+        ``per_attractor[k]`` the visits counted on states of attractor k, ``outside`` those on states of no found
+        attractor (``dropped`` visits are in neither; ``per_attractor.sum() + outside + dropped == visits``). Host
+        lookup of the census' states in :meth:`state_set`."""
+        labels = self.state_set(device=None).lookup(census_result.states)
+        counts = np.asarray(census_result.counts, dtype=np.uint64)
+        per = np.zeros(len(self.attractors), dtype=np.uint64)
+        np.add.at(per, labels[labels >= 0], counts[labels >= 0])
+        return per, int(counts[labels < 0].sum())
+
 
 def _known(found, s) -> int:
     """Index of the found attractor holding state ``s``, or -1. Attractors are disjoint, so one state decides."""

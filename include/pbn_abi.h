@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define PBN_ABI_VERSION 21
+#define PBN_ABI_VERSION 22
 
 enum {
     PBN_OK = 0,
@@ -497,6 +497,67 @@ int pbn_env_set_reset_device(pbn_batch *b, const uint64_t *d_rows, const uint32_
 /* Waits for the batch's stream; PBN_E_RANGE if an env was skipped by either call since the last check (the flag is
  * cleared: reported once). */
 int pbn_env_set_check(pbn_batch *b);
+
+/* ---- state census: statistical_attractors (pbn_target.py:538-560, pbn_target_multi.py:465-487), whose
+ * `state_log[tuple(state)] += 1` over 100 resets x 1,000 steps becomes an exact device table of visit counts keyed by
+ * the packed full state (W = 1..8 words, both network kinds), fed by every env of a batch in one launch ----
+ * One uint64 count per distinct state, up to max_states of them (at most PBN_CENSUS_MAX_STATES = 2^24, what a
+ * pbn_stateset takes); the hash table has the power of two >= 2 max_states slots, at least 64. Counts accumulate over
+ * pbn_census_run_device calls until pbn_census_clear.
+ * Overflow is counted, never silent: the census reports the first max_states states it took in, and a visit of any
+ * other state adds to `dropped`. Guarantees:
+ *   (a) n_states <= max_states;
+ *   (b) sum of the counts + dropped == visits, exactly;
+ *   (c) dropped == 0: every count is exact;
+ *   (d) dropped > 0: every reported count is <= the true count of that state. Up to 2^19 states past max_states are
+ *       still held (unreported, their visits counted as dropped), so that no state is inserted twice. Once those
+ *       entries are used up too, or every slot of a state's probe sequence holds another state, a visit is dropped on
+ *       the spot. Only then can a reported state's count fall short: a lane that finds no free entry looks at the
+ *       slot once more, and a publish of the same state that lands after that second look is missed.
+ * One census is fed by one batch at a time: the caller serialises pbn_census_* calls on a census, and two batches
+ * feeding one census must not overlap (wait for the first batch's stream, or use one stream). */
+typedef struct pbn_census pbn_census;
+typedef struct {
+    int32_t n_nodes, n_words, device; /* device -1: a host-only handle */
+    uint64_t max_states, table_slots;
+    uint64_t n_states; /* distinct states held */
+    uint64_t visits;   /* sample points of every run since the last clear: n_envs x samples per run */
+    uint64_t dropped;
+} pbn_census_info;
+#define PBN_CENSUS_MAX_STATES (1ull << 24)
+#define PBN_CENSUS_MAX_UPDATES 65536u
+/* The defaultdict(int) of pbn_target.py:546 / pbn_target_multi.py:473, empty. n_nodes outside [1, 512] or max_states
+ * outside [1, PBN_CENSUS_MAX_STATES]: PBN_E_INVALID. device == -1: a host-only handle (the pbn_stateset_create
+ * precedent): the argument checks of pbn_census_run_device run without a GPU, and the call then returns PBN_E_STATE. */
+int pbn_census_create(int32_t n_nodes, int device, uint64_t max_states, pbn_census **out);
+void pbn_census_destroy(pbn_census *c);
+/* Empties the table and zeroes visits and dropped; waits for the last run first. */
+int pbn_census_clear(pbn_census *c);
+/* Waits for the stream the last run went to. */
+int pbn_census_get_info(pbn_census *c, pbn_census_info *info);
+/* The loop of pbn_target.py:548-556 (`state_log[tuple(state)] += 1; self.step(...)`) for every env of the batch, one
+ * launch, asynchronous, on the batch's stream. Env e makes n_updates updates, update i with exactly the draw pbn_step
+ * makes for update update_count + i of the env: afterwards the state is bit for bit pbn_step(n_updates)'s and the
+ * batch's update counter has advanced by n_updates, so the call mixes freely with pbn_step, pbn_flip and the env
+ * calls. "The state after i updates" is counted for i = first, first + stride, first + 2 stride, ... <= n_updates;
+ * first = 0 counts the state as it was before the call (the reference logs before it steps); n_updates = 0 with
+ * first = 0 counts the current state and moves nothing. mask_words (host [W], NULL = every node): the key is
+ * state & mask, a projection onto a node subset.
+ * PBN_E_INVALID, before anything is launched or any counter moves: n_updates above PBN_CENSUS_MAX_UPDATES (longer runs
+ * loop on the host), stride == 0, first > n_updates, mask bits past node N-1, a batch of another n_nodes or device.
+ * A host-only census: PBN_E_STATE. */
+int pbn_census_run_device(pbn_batch *b, pbn_census *c, uint32_t n_updates, uint32_t first, uint32_t stride,
+                          const uint64_t *mask_words);
+/* `state_log.items()` (pbn_target.py:558): the states held [n][W] and their counts [n], in no particular order; waits
+ * for the last run. *n_states is always set; with states and counts NULL nothing else happens; cap < *n_states:
+ * PBN_E_INVALID. Either array may be NULL. */
+int pbn_census_read(pbn_census *c, uint64_t *states, uint64_t *counts, uint64_t cap, uint64_t *n_states);
+/* Measurement, no reference counterpart; either pointer may be NULL. *adds: count adds the runs issued since the last
+ * clear. A lane adds once per run of equal consecutive keys, so adds / visits is the share of sample points that
+ * touched memory. *entries: entries taken from the end of the key array since the last clear: the states held
+ * (n_states, plus those past max_states) and the entries taken in vain by lanes that lost a publish race, at most one
+ * per lane of a launch and handed out again by later launches. Waits for the last run. */
+int pbn_census_get_stats(pbn_census *c, uint64_t *adds, uint64_t *entries);
 
 #ifdef __cplusplus
 }
