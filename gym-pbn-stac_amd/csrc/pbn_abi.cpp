@@ -216,6 +216,17 @@ int pbn_net_unstable(const pbn_net* n, int32_t graph, const uint64_t* states, ui
     return 0;
 }
 
+int pbn_net_edge_mass(const pbn_net* n, int32_t graph, const uint64_t* states, uint64_t n_states, uint64_t* mass) {
+    CHECK_NN(n, "net");
+    CHECK_NN(states, "states");
+    CHECK_NN(mass, "mass");
+    if (n->L.kind == KIND_PROB_TABLE && graph != PBN_TABLE_GRAPH_STG && graph != PBN_TABLE_GRAPH_STEP)
+        return fail(PBN_E_INVALID, "graph=%d is neither PBN_TABLE_GRAPH_STG nor PBN_TABLE_GRAPH_STEP", (int)graph);
+    if (n_states < 1 || n_states > (1ull << 28)) return fail(PBN_E_INVALID, "n_states outside [1, 2^28]");
+    net_edge_mass(n, graph, states, n_states, mass);
+    return 0;
+}
+
 void pbn_net_destroy(pbn_net* n) {
     if (!n) return;
     n->dev_image.release();

@@ -21,6 +21,7 @@
 #include "pbn_env_plan.hpp"
 #include "pbn_step_plan.hpp"
 #include "pbn_reach_rule.hpp"
+#include "pbn_mass_rule.hpp"
 #include "pbn_stateset.hpp"
 
 using namespace pbn;
@@ -77,6 +78,7 @@ PBN_HIDDEN int build_envcfg_image(const pbn_net& net, const pbn_envcfg_desc* d, 
 PBN_HIDDEN std::vector<uint8_t> env_gen_image(const pbn_envcfg* cfg, uint32_t erec_shift);
 PBN_HIDDEN uint64_t net_select_u32(const pbn_net* n, int32_t node, uint32_t a);
 PBN_HIDDEN void net_unstable(const pbn_net* n, int graph, const uint64_t* states, uint64_t n_states, uint64_t* masks);
+PBN_HIDDEN void net_edge_mass(const pbn_net* n, int graph, const uint64_t* states, uint64_t n_states, uint64_t* mass);
 
 #ifndef PBN_HOST_NO_HIP
 #define HIP_TRY(expr)                                                                              \

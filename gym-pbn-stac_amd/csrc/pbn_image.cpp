@@ -198,6 +198,22 @@ void net_unstable(const pbn_net* n, int graph, const uint64_t* states, uint64_t 
     }
 }
 
+// The law of the update (pbn_mass_rule.hpp, the definition k_stg_rows evaluates) on the host copy of the u64 image:
+// mass [S][N], the edge mass of node i at states [S][W]. graph as for net_unstable.
+void net_edge_mass(const pbn_net* n, int graph, const uint64_t* states, uint64_t n_states, uint64_t* mass) {
+    const uint32_t N = (uint32_t)n->L.n_nodes, W = (uint32_t)n->W;
+    const bool table = n->L.kind == KIND_PROB_TABLE;
+    const uint32_t first = table ? table_graph_first_node(graph) : 0u;
+    const uint8_t* im = n->image.data();
+    for (uint64_t e = 0; e < n_states; e++) {
+        const uint64_t* s = states + e * W;
+        auto bit = [s](uint32_t j) { return (uint32_t)(s[j >> 6] >> (j & 63u)) & 1u; };
+        for (uint32_t i = 0; i < N; i++)
+            mass[e * N + i] = table ? edge_mass<KIND_PROB_TABLE>(bit, i, first, im, n->L)
+                                    : edge_mass<KIND_PREDICTOR_MIX>(bit, i, first, im, n->L);
+    }
+}
+
 // The env config's image: the network's u64 image, the attractor cubes, the target and the per-node
 // counter deltas; `c` also takes the reset cubes and the scalars of `d`.
 int build_envcfg_image(const pbn_net& net, const pbn_envcfg_desc* d, pbn_envcfg* c) {

@@ -452,8 +452,25 @@ struct EnvSetResetArgs {
     int32_t* error;            // EnvSetArgs::error: set to 1 by an env whose source names no non-empty attractor
 };
 
+// The exact transition graph of a state set (k_stg_rows, pbn_stg.hip): for rows [first_row, first_row +
+// n_rows) of `states`, the edge mass (pbn_mass_rule.hpp) of every node and the row of the neighbour it leads to.
+constexpr uint64_t STG_MAX_CELLS = 1ull << 31;  // n_rows * N of one call: a cell index fits 32 bits
+
+struct StgArgs {
+    const void* img;            // network image (the u64 image of either kind; L.kind selects the mass rule)
+    NetLayout L;
+    uint32_t first_node;        // lowest node that may move (ReachArgs::first_node)
+    const uint64_t* states;     // [S][W] the set's rows, in row order
+    SetView set;                // the same rows as a table, label = row index
+    uint32_t first_row;
+    uint64_t n_cells;           // n_rows * N <= STG_MAX_CELLS
+    unsigned long long* mass;   // [n_rows][N]
+    int32_t* succ;              // [n_rows][N]: the neighbour's row; -1 a leak; the row itself where mass == 0
+    unsigned long long* leaks;  // += the -1 entries written
+};
+
 // Launchers (pbn_step.hip, pbn_state.hip, pbn_env.hip, pbn_group.hip, pbn_mt.hip, pbn_ssd.hip, pbn_sync.hip, pbn_reach.hip,
-// pbn_tenv.hip, pbn_tenv_macro.hip, pbn_env_set.hip). Return hipError_t as int.
+// pbn_tenv.hip, pbn_tenv_macro.hip, pbn_env_set.hip, pbn_stg.hip). Return hipError_t as int.
 // The lane-per-env kernels (pbn_lane_env.hpp): each file picks its kernel (nullptr: none for that shape), one
 // launcher and one occupancy query serve them all. plane_off: the LDS byte offset of the kernel's state planes;
 // args: the kernel's argument struct.
@@ -466,6 +483,9 @@ int launch_env_set_reset(int W, const EnvSetResetArgs& a, void* stream);
 enum { REACH_K_UNSTABLE = 0, REACH_K_SEED, REACH_K_EXPAND, REACH_K_BACK_START, REACH_K_BACK, REACH_K_HULL };
 int launch_reach(int W, int which, const ReachArgs& a, int grid, void* stream);
 int launch_set_lookup(int W, const SetLookupArgs& a, void* stream);
+void* stg_rows_kernel(int W, int kind);  // pbn_stg.hip; nullptr: none for that shape
+int launch_stg_rows(void* kernel, const StgArgs& a, int grid, void* stream);
+int max_blocks_stg_rows(void* kernel, uint32_t image_bytes, int* blocks_per_cu);
 int launch_bump(uint64_t* p, uint64_t k, void* stream);
 int launch_set_counters(uint64_t* p, uint64_t v, uint32_t n, void* stream);
 int launch_step(int W, const StepArgs& a, int store_mode, int replay, int sb, int grid, void* stream);

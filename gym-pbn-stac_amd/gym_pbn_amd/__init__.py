@@ -43,6 +43,10 @@ def __getattr__(name):
         from . import census
 
         return getattr(census, name)
+    if name in ("TransitionGraph", "host_edge_mass"):
+        from . import transition
+
+        return getattr(transition, name)
     if name in ("TorchVecPBNEnv", "TorchVecPBNTargetMultiEnv", "TorchVecPBNTargetMultiSetEnv"):
         from . import torch_env
 

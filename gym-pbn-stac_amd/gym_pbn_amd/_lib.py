@@ -119,6 +119,16 @@ class CensusInfo(C.Structure):
 CENSUS_MAX_STATES = 1 << 24     # PBN_CENSUS_MAX_STATES
 CENSUS_MAX_UPDATES = 65536      # PBN_CENSUS_MAX_UPDATES: updates per pbn_census_run_device call
 
+class StgInfo(C.Structure):
+    _fields_ = [
+        ("n_nodes", C.c_int32), ("n_words", C.c_int32), ("first_node", C.c_int32), ("n_movable", C.c_int32),
+        ("device", C.c_int32), ("table_graph", C.c_int32), ("n_states", C.c_uint64), ("leaks", C.c_uint64),
+    ]
+
+
+STG_MAX_STATES = 1 << 24        # PBN_STG_MAX_STATES
+STG_MAX_CELLS = 1 << 31         # PBN_STG_MAX_CELLS: n_rows * n_nodes of one pbn_stg_rows_device call
+
 # pbn_tenv_macro_device: modes (PBN_MACRO_*) and the cap on t_max (PBN_TENV_MACRO_MAX_T)
 from .macro_env import MACRO_INTERVAL, MACRO_TRIGGER, TENV_MACRO_MAX_T  # noqa: E402,F401
 
@@ -208,6 +218,12 @@ SIGNATURES = {
     "pbn_census_run_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _u64p]),
     "pbn_census_read": (C.c_int, [_vp, _u64p, _u64p, C.c_uint64, _u64p]),
     "pbn_census_get_stats": (C.c_int, [_vp, _u64p, _u64p]),
+    "pbn_net_edge_mass": (C.c_int, [_vp, C.c_int32, _u64p, C.c_uint64, _u64p]),
+    "pbn_stg_create": (C.c_int, [_vp, C.c_int, C.c_int32, _u64p, C.c_uint64, _PP]),
+    "pbn_stg_destroy": (None, [_vp]),
+    "pbn_stg_get_info": (C.c_int, [_vp, C.POINTER(StgInfo)]),
+    "pbn_stg_clear_leaks": (C.c_int, [_vp]),
+    "pbn_stg_rows_device": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _vp, _vp]),
 }
 
 

@@ -155,6 +155,25 @@ def host_unstable(net, states, table_graph: Optional[str] = None) -> np.ndarray:
     return out
 
 
+def host_edge_mass(net, states, table_graph: Optional[str] = None) -> np.ndarray:
+    """The law behind :func:`host_unstable`'s support (``pbn_net_edge_mass``, ``csrc/pbn_mass_rule.hpp``; module
+    :mod:`gym_pbn_amd.transition`): the edge masses ``[S][N]`` uint64 of packed ``states`` ``[S][W]``, each an integer
+    in ``[0, 2**53]`` -- in units of ``2**-53`` the probability that node ``i`` flips given that it is the node updated.
+    The same rule definition ``k_stg_rows`` evaluates, run over the host copy of the network image; ``mass > 0``
+    exactly where :func:`host_unstable` sets the bit. ``table_graph`` is required for a truth-table network
+    (``"step"``: node 0 has mass 0) and ignored for a predictor-mix one."""
+    net = net if isinstance(net, Net) else Net(net)
+    graph = 0
+    if net.kind == KIND_PROB_TABLE:
+        if table_graph not in TABLE_GRAPHS:
+            raise ValueError(f"table_graph={table_graph!r}: expected one of {sorted(TABLE_GRAPHS)}")
+        graph = TABLE_GRAPHS[table_graph]
+    w = np.ascontiguousarray(states, dtype=np.uint64).reshape(-1, net.n_words)
+    out = np.empty((w.shape[0], net.n_nodes), dtype=np.uint64)
+    L.check(L.lib.pbn_net_edge_mass(net.handle, graph, L.ptr(w, L._u64p), w.shape[0], L.ptr(out, L._u64p)))
+    return out
+
+
 # ---------------------------------------------------------------- host helpers
 def sort_rows(words: np.ndarray) -> np.ndarray:
     """Rows ``[S][W]`` sorted as integers (word ``W-1`` most significant)."""
@@ -234,13 +253,16 @@ class AttractorResult:
     ``attractors``: packed ``[S_k][W]`` arrays, rows sorted as integers, ordered by (size, smallest
     state). ``seed_counts[k]``: seeds that ended in attractor k (a seed that reaches several is
     counted for one of them). ``incomplete``: closures that did not fit ``max_states``, as dicts
-    ``{"seed", "n_seen", "hull", "n_seeds"}`` (``hull``: the cube of the states seen).
+    ``{"seed", "n_seen", "hull", "n_seeds"}`` (``hull``: the cube of the states seen). ``network`` / ``table_graph``:
+    what the attractors were found on (``None`` for a result built by hand), for :meth:`transition_graph`.
     """
 
     n_nodes: int
     attractors: List[np.ndarray] = field(default_factory=list)
     seed_counts: List[int] = field(default_factory=list)
     incomplete: List[dict] = field(default_factory=list)
+    network: object = None  # the Net the attractors were found on, and its table graph (find_attractors sets both)
+    table_graph: Optional[str] = None
 
     def all_attractors(self, max_cubes: int = MAX_ENV_CUBES) -> list:
         """The reference's ``all_attractors``: per attractor a list of cube tuples (ints / ``'*'``),
@@ -275,6 +297,17 @@ class AttractorResult:
         per = np.zeros(len(self.attractors), dtype=np.uint64)
         np.add.at(per, labels[labels >= 0], counts[labels >= 0])
         return per, int(counts[labels < 0].sum())
+
+    def transition_graph(self, k: int, device: Optional[int] = 0, network=None):
+        """The exact weighted graph of attractor ``k`` (:class:`gym_pbn_amd.transition.TransitionGraph`): closed, so
+        ``stationary()`` is the distribution inside it. The network is the one :func:`find_attractors` ran on, or
+        ``network`` for a result built by hand."""
+        from .transition import TransitionGraph
+
+        net = self.network if network is None else network
+        if net is None:
+            raise ValueError("this AttractorResult carries no network: pass network=")
+        return TransitionGraph(net, self.attractors[k], table_graph=self.table_graph, device=device)
 
 
 def _known(found, s) -> int:
@@ -344,7 +377,7 @@ def find_attractors(network, n_seeds: int = 4096, burn_in: Optional[int] = None,
     uniq, mult = np.unique(seeds, axis=0, return_counts=True)
     owner = np.full(len(uniq), -1, dtype=np.int64)  # attractor of each distinct seed; -2 = incomplete
     found: List[np.ndarray] = []
-    res = AttractorResult(N)
+    res = AttractorResult(N, network=net, table_graph=graph)
 
     def note_incomplete(k, info):
         n_seen, all_w, any_w = info
@@ -443,6 +476,6 @@ def find_state_attractors(network, device: int = 0, seed: int = 0) -> list:
     return res.states_lists()
 
 
-__all__ = ["ReachSet", "AttractorResult", "host_unstable", "find_attractors", "cube_cover", "expand_cubes", "hull_cube", "rows_in",
+__all__ = ["ReachSet", "AttractorResult", "host_unstable", "host_edge_mass", "find_attractors", "cube_cover", "expand_cubes", "hull_cube", "rows_in",
            "sort_rows", "resolve_all_attractors", "find_state_attractors", "MAX_ENV_CUBES", "MAX_ENV_STATES",
            "TABLE_GRAPHS"]

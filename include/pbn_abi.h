@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define PBN_ABI_VERSION 22
+#define PBN_ABI_VERSION 23
 
 enum {
     PBN_OK = 0,
@@ -147,6 +147,12 @@ int pbn_net_select_u32(const pbn_net *net, int32_t node, uint32_t a, uint64_t *r
  * PREDICTOR_MIX networks have one graph: `graph` is ignored. */
 enum { PBN_TABLE_GRAPH_STG = 1, PBN_TABLE_GRAPH_STEP = 2 };
 int pbn_net_unstable(const pbn_net *net, int32_t graph, const uint64_t *states, uint64_t n_states, uint64_t *masks);
+/* The law behind that support (see "exact transition graph" below), host side, no device: states [S][W] -> mass
+ * [S][N] uint64 in [0, 2^53], the probability in units of 2^-53 that node i takes the value 1 - x_i at that state
+ * given that node i is the one updated. It is the one definition k_stg_rows evaluates (csrc/pbn_mass_rule.hpp), and
+ * mass > 0 exactly where pbn_net_unstable sets the bit. `graph` as for pbn_net_unstable; under PBN_TABLE_GRAPH_STEP
+ * node 0 has mass 0. */
+int pbn_net_edge_mass(const pbn_net *net, int32_t graph, const uint64_t *states, uint64_t n_states, uint64_t *mass);
 
 /* ---- batches of independent envs (the reference holds one Graph per env) ---- */
 /* Tuning knobs, read from the environment once here (measurement and tests only):
@@ -558,6 +564,50 @@ int pbn_census_read(pbn_census *c, uint64_t *states, uint64_t *counts, uint64_t 
  * (n_states, plus those past max_states) and the entries taken in vain by lanes that lost a publish race, at most one
  * per lane of a launch and handed out again by later launches. Waits for the last run. */
 int pbn_census_get_stats(pbn_census *c, uint64_t *adds, uint64_t *entries);
+
+/* ---- exact transition graph of a state set: Graph.getNextStates (bittner/base.py:221-242, `{next_state: prob}` of
+ * one state; genSTG :199-218 builds the weighted graph from it), PBN._compute_next_states (common/pbn.py:186-199) and
+ * PBCN._async_compute_next_states (common/pbcn.py:72-93) for truth tables, for every state of an enumerated set in
+ * one launch ----
+ * The reference loops over 2^N states in Python; here the set is whatever the caller enumerated (an attractor of
+ * pbn_reach_*, a closure, a census' states), S <= PBN_STG_MAX_STATES rows, and the graph is two dense arrays:
+ *   mass [S][N] uint64  the edge mass of node i at row s (pbn_net_edge_mass: an exact integer in [0, 2^53]);
+ *   succ [S][N] int32   the row of x_s ^ (1 << i) where mass > 0 and that state is a member; -1 where mass > 0 and
+ *                       it is not (a leak: the set is not closed under the dynamics); s itself where mass == 0 (no
+ *                       edge, and no probe is made for it).
+ * The probability of the edge is mass / (2^53 * n_movable): the updated node is drawn uniformly from the n_movable =
+ * N - first_node nodes that may move (base.py:308 randint(0, N-1), getNextStates' 1 / len(state); pbn.py:131
+ * randint(1, N-1) for PBN_TABLE_GRAPH_STEP). For PBN_TABLE_GRAPH_STG the uniform choice is this library's: the
+ * reference's async STG carries prob_true unnormalised.
+ * Both network kinds, W = 1..8 words. */
+#define PBN_STG_MAX_STATES ((uint64_t)1 << 24)
+#define PBN_STG_MAX_CELLS ((uint64_t)1 << 31)
+typedef struct pbn_stg pbn_stg;
+typedef struct {
+    int32_t n_nodes, n_words, first_node, n_movable;
+    int32_t device;      /* -1: a host-only handle */
+    int32_t table_graph; /* PBN_TABLE_GRAPH_*, 0 for a predictor-mix network */
+    uint64_t n_states;
+    uint64_t leaks;      /* -1 entries written by pbn_stg_rows_device since the last pbn_stg_clear_leaks */
+} pbn_stg_info;
+/* states [S][W] host, 1 <= S <= PBN_STG_MAX_STATES; row r of the graph is states[r]. The handle keeps the states and a
+ * pbn_stateset-style table over them whose label is the row index (csrc/pbn_stateset.hpp, built as pbn_stateset_create
+ * builds it). A row given twice, or bits set past node N-1: PBN_E_INVALID. `graph` as for pbn_net_unstable:
+ * PBN_TABLE_GRAPH_STG / _STEP for a PROB_TABLE network (anything else PBN_E_INVALID), ignored for PREDICTOR_MIX.
+ * device == -1: a host-only handle (the pbn_stateset_create precedent): pbn_stg_get_info works, the argument checks of
+ * pbn_stg_rows_device run without a GPU and the call then returns PBN_E_STATE. */
+int pbn_stg_create(const pbn_net *net, int device, int32_t graph, const uint64_t *states, uint64_t n_states,
+                   pbn_stg **out);
+void pbn_stg_destroy(pbn_stg *g);
+/* Waits for the rows launched so far (it reads the leak counter). */
+int pbn_stg_get_info(pbn_stg *g, pbn_stg_info *info);
+int pbn_stg_clear_leaks(pbn_stg *g);
+/* Fills d_mass [n_rows][N] uint64 and d_succ [n_rows][N] int32 (device memory of the graph's device, 8- / 4-byte
+ * aligned) for rows [first_row, first_row + n_rows), and adds the -1 entries it wrote to the leak counter. One launch
+ * on the device's default stream, asynchronous. The caller chunks by rows, so its memory stays bounded: n_rows * N
+ * above PBN_STG_MAX_CELLS is PBN_E_INVALID. Rows past S: PBN_E_RANGE; a NULL array: PBN_E_INVALID; a host-only
+ * handle: PBN_E_STATE; n_rows == 0: nothing is launched. */
+int pbn_stg_rows_device(pbn_stg *g, uint64_t first_row, uint64_t n_rows, void *d_mass, void *d_succ);
 
 #ifdef __cplusplus
 }
