@@ -7,22 +7,6 @@
 static_assert(PBN_STG_MAX_STATES == STATESET_MAX_STATES && PBN_STG_MAX_CELLS == STG_MAX_CELLS,
               "pbn_abi.h, pbn_stateset.hpp and pbn_params.hpp name the same caps");
 
-// The graph of one state set of one network. Host-only (device -1): the shape and the argument checks, no device memory.
-struct pbn_stg {
-    pbn_net* net = nullptr;
-    int device = -1, W = 0;
-    int graph = TABLE_GRAPH_NONE;  // truth-table networks: PBN_TABLE_GRAPH_STG / _STEP
-    uint64_t n_states = 0;
-    StateSetTable t;            // label = row index
-    DevBuf rows, meta, keys;    // the states in row order, and the table over them
-    DevBuf leaks;               // one uint64: the -1 entries written since the last pbn_stg_clear_leaks
-    const void* d_image = nullptr;
-    void* kernel = nullptr;
-    int n_cu = 0, bpc = 1;
-    int grid_cap = 0;  // PBNSIM_STG_GRID (tests: a small graph walks the grid-stride loop), 0 = what is resident
-    uint32_t first_node() const { return net->L.kind == KIND_PROB_TABLE ? table_graph_first_node(graph) : 0u; }
-};
-
 extern "C" {
 
 int pbn_stg_create(const pbn_net* net_c, int device, int32_t graph, const uint64_t* states, uint64_t n_states,

@@ -432,6 +432,29 @@ inline int launch_lane_env_step(pbn_batch* b, const char* name, void* kernel, ui
     return timed_launch(b, name, [&] { return launch_lane_env(kernel, b->W, plane_off, grid, b->stream, &a); });
 }
 
+// The graph of one state set of one network (pbn_abi_stg.cpp; the control entry points over it: pbn_abi_control.cpp).
+// Host-only (device -1): the shape and the argument checks, no device memory.
+struct pbn_stg {
+    pbn_net* net = nullptr;
+    int device = -1, W = 0;
+    int graph = TABLE_GRAPH_NONE;  // truth-table networks: PBN_TABLE_GRAPH_STG / _STEP
+    uint64_t n_states = 0;
+    StateSetTable t;            // label = row index
+    DevBuf rows, meta, keys;    // the states in row order, and the table over them
+    DevBuf leaks;               // one uint64: the -1 entries written since the last pbn_stg_clear_leaks
+    const void* d_image = nullptr;
+    void* kernel = nullptr;
+    int n_cu = 0, bpc = 1;
+    int grid_cap = 0;  // PBNSIM_STG_GRID (tests: a small graph walks the grid-stride loop), 0 = what is resident
+    enum { CTL_FLIP = 0, CTL_EXPECT, CTL_BACKUP, CTL_KERNELS };
+    struct Ctl {  // the kernels of pbn_control.hip for this graph's shape, picked and asked for occupancy once
+        void* kernel = nullptr;
+        int bpc = 0;  // 0: not asked yet
+    } ctl[CTL_KERNELS];
+    uint32_t first_node() const { return net->L.kind == KIND_PROB_TABLE ? table_graph_first_node(graph) : 0u; }
+    SetView view() const { return SetView{(const uint32_t*)meta.p, (const uint64_t*)keys.p, t.slots}; }
+};
+
 // Attractor discovery (pbn_reach.hip); entry points in pbn_abi_reach.cpp.
 struct pbn_reach {
     pbn_net* net = nullptr;

@@ -469,8 +469,42 @@ struct StgArgs {
     unsigned long long* leaks;  // += the -1 entries written
 };
 
+// Optimal control over a transition graph (pbn_control.hip). The cell index row * N + node is 64-bit
+// in all three: S * N reaches 2^33.
+struct StgFlipArgs {
+    const uint64_t* states;        // [S][W] the set's rows, in row order
+    SetView set;                   // the same rows as a table, label = row index
+    uint64_t first_row, n_cells;   // rows [first_row, first_row + n_cells / N)
+    uint32_t n_nodes;
+    uint64_t allowed[MAX_WORDS];   // bit i: node i may be flipped (the first W words are read)
+    int32_t* nbr;                  // [n_rows][N]: the row of x_row ^ bit(i); -1 outside the set or not allowed
+};
+
+struct StgExpectArgs {
+    const unsigned long long* mass;  // [S][N]
+    const int32_t* succ;             // [S][N]
+    const double* v;                 // [S]
+    double* out;                     // [S] E[v(next) | s]
+    const double* pen;               // [S] or null
+    double cost;
+    double* out_pen;                 // [S] out - cost * pen (pen non-null)
+    uint64_t n_states;
+    uint32_t n_nodes;
+    double n_movable;
+};
+
+struct StgBackupArgs {
+    const int32_t* nbr;  // [S][N]
+    const double* u;     // [S] the no-op's value
+    const double* ua;    // [S] the value of arriving at a row by a flip
+    double* v;           // [S] the max
+    int32_t* policy;     // [S] -1 the no-op, else the node
+    uint64_t n_states;
+    uint32_t n_nodes;
+};
+
 // Launchers (pbn_step.hip, pbn_state.hip, pbn_env.hip, pbn_group.hip, pbn_mt.hip, pbn_ssd.hip, pbn_sync.hip, pbn_reach.hip,
-// pbn_tenv.hip, pbn_tenv_macro.hip, pbn_env_set.hip, pbn_stg.hip). Return hipError_t as int.
+// pbn_tenv.hip, pbn_tenv_macro.hip, pbn_env_set.hip, pbn_stg.hip, pbn_control.hip). Return hipError_t as int.
 // The lane-per-env kernels (pbn_lane_env.hpp): each file picks its kernel (nullptr: none for that shape), one
 // launcher and one occupancy query serve them all. plane_off: the LDS byte offset of the kernel's state planes;
 // args: the kernel's argument struct.
@@ -486,6 +520,13 @@ int launch_set_lookup(int W, const SetLookupArgs& a, void* stream);
 void* stg_rows_kernel(int W, int kind);  // pbn_stg.hip; nullptr: none for that shape
 int launch_stg_rows(void* kernel, const StgArgs& a, int grid, void* stream);
 int max_blocks_stg_rows(void* kernel, uint32_t image_bytes, int* blocks_per_cu);
+// pbn_control.hip: each picks its kernel (nullptr: none for that shape; G, one_cell: ControlPlan's G and cells_per_lane == 1),
+// one launcher (BLOCK threads, no LDS; args: the kernel's argument struct) and one occupancy query serve the three
+void* stg_flip_rows_kernel(int W);
+void* stg_expect_kernel(uint32_t G, bool one_cell);
+void* stg_backup_kernel(uint32_t G, bool one_cell);
+int launch_control(void* kernel, int grid, void* stream, void* args);
+int max_blocks_control(void* kernel, int* blocks_per_cu);
 int launch_bump(uint64_t* p, uint64_t k, void* stream);
 int launch_set_counters(uint64_t* p, uint64_t v, uint32_t n, void* stream);
 int launch_step(int W, const StepArgs& a, int store_mode, int replay, int sb, int grid, void* stream);

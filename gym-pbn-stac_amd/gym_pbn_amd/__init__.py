@@ -47,6 +47,10 @@ def __getattr__(name):
         from . import transition
 
         return getattr(transition, name)
+    if name in ("ControlProblem", "ControlSolution", "host_backup", "host_expect"):
+        from . import control
+
+        return getattr(control, name)
     if name in ("TorchVecPBNEnv", "TorchVecPBNTargetMultiEnv", "TorchVecPBNTargetMultiSetEnv"):
         from . import torch_env
 

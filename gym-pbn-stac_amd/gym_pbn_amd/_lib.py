@@ -224,6 +224,10 @@ SIGNATURES = {
     "pbn_stg_get_info": (C.c_int, [_vp, C.POINTER(StgInfo)]),
     "pbn_stg_clear_leaks": (C.c_int, [_vp]),
     "pbn_stg_rows_device": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _vp, _vp]),
+    "pbn_stg_flip_rows_device": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _u64p, _vp]),
+    "pbn_stg_expect_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_double, _vp]),
+    "pbn_stg_backup_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "pbn_stg_lookup_device": (C.c_int, [_vp, _vp, C.c_uint64, _vp]),
 }
 
 

@@ -18,7 +18,9 @@ a closure, the states of a census -- as two dense device arrays filled in one la
 **Exact**: ``mass``, ``succ``, ``leaks``, ``closed`` -- integers, equal bit for bit to :func:`host_edge_mass` and a
 host lookup. **Float64**: :meth:`TransitionGraph.probabilities`, :meth:`~TransitionGraph.pull`,
 :meth:`~TransitionGraph.push`, :meth:`~TransitionGraph.stationary`, :meth:`~TransitionGraph.next_states` -- torch /
-Python arithmetic on the integer arrays.
+Python arithmetic on the integer arrays -- and :meth:`~TransitionGraph.expect`, ``pull`` as one fused kernel
+(``csrc/pbn_control.hip``; what :mod:`gym_pbn_amd.control` iterates). :meth:`~TransitionGraph.row_of` names the row of
+device state words.
 
 **Node choice.** The probability of an edge is ``mass / (2**53 * n_movable)``: the updated node is drawn uniformly
 from the movable nodes -- all ``N`` for a predictor-mix network (``Graph.step``'s ``randint(0, N-1)``,
@@ -201,6 +203,77 @@ class TransitionGraph:
         p = self.probabilities()
         v = torch.as_tensor(v, dtype=torch.float64, device=p.device).reshape(self.n_states)
         return (p * v[self.succ.long()]).sum(dim=1) + (1.0 - p.sum(dim=1)) * v
+
+    # ------------------------------------------------------------ fused kernels on the integer arrays (csrc/pbn_control.hip)
+    def _on_default_stream(self, dev):
+        """A context that orders the library's default-stream launches against torch's current stream, as
+        :meth:`_fill` does, and makes the default stream torch's current one inside, so that torch ops between two
+        launches (a sweep's ``h``) run in order with them."""
+        import contextlib
+
+        import torch
+
+        @contextlib.contextmanager
+        def ordered():
+            cur, dflt = torch.cuda.current_stream(dev), torch.cuda.default_stream(dev)
+            if cur == dflt:
+                yield
+                return
+            dflt.wait_stream(cur)
+            try:
+                with torch.cuda.stream(dflt):
+                    yield
+            finally:
+                cur.wait_stream(dflt)
+
+        return ordered()
+
+    def _expect_into(self, v, out, pen=None, cost: float = 0.0, out_pen=None):
+        """``k_stg_expect`` on contiguous float64 device tensors ``[S]``; no checks, no ordering: the caller's."""
+        mass, succ = self.mass, self.succ
+        L.check(L.lib.pbn_stg_expect_device(self._h, mass.data_ptr(), succ.data_ptr(), v.data_ptr(), out.data_ptr(),
+                                            None if pen is None else pen.data_ptr(), float(cost),
+                                            None if out_pen is None else out_pen.data_ptr()))
+
+    def expect(self, v, pen=None, cost: float = 0.0):
+        """:meth:`pull` in one fused launch (``k_stg_expect``): ``v[s] + (sum_i mass[s][i] * (v[succ[s][i]] - v[s])) *
+        2**-53 / n_movable``, read from the integer arrays in one pass with no ``[S][N]`` temporary. The same real
+        number as :meth:`pull`, rounded differently (within ``(2 N + 8) * 2**-53 * max|v|`` of it); a constant comes
+        back exactly; the result is bit-identical from call to call and under any grid. With ``pen`` ``[S]`` it
+        returns ``(out, out - cost * pen)``, both written in the same pass. Raises ``ValueError`` unless the set is
+        closed."""
+        import torch
+
+        self._need_closed("expect")
+        dev = self.mass.device
+        v = torch.as_tensor(v, dtype=torch.float64, device=dev).reshape(self.n_states).contiguous()
+        out = torch.empty_like(v)
+        out_pen = None
+        if pen is not None:
+            pen = torch.as_tensor(pen, dtype=torch.float64, device=dev).reshape(self.n_states).contiguous()
+            out_pen = torch.empty_like(v)
+        with self._on_default_stream(dev):
+            self._expect_into(v, out, pen, cost, out_pen)
+        return out if pen is None else (out, out_pen)
+
+    def row_of(self, words):
+        """The row of each state of ``words`` (device int64 ``[n][W]``, e.g. ``observation_words()`` of a device env):
+        device int32 ``[n]``, ``-1`` for a state that is no row. One launch of the state set's lookup kernel over the
+        graph's own table."""
+        import torch
+
+        if self.device is None:
+            raise L.PbnError(L.PBN_E_STATE, "the transition graph is a host-only handle (device=None)")
+        dev = torch.device("cuda", self.device)
+        w = torch.as_tensor(words, device=dev)
+        if w.dtype != torch.int64:
+            raise ValueError(f"words: int64 [n][{self.n_words}] on the device, not {w.dtype}")
+        w = w.reshape(-1, self.n_words).contiguous()
+        out = torch.empty(w.shape[0], dtype=torch.int32, device=dev)
+        if w.shape[0]:
+            with self._on_default_stream(dev):
+                L.check(L.lib.pbn_stg_lookup_device(self._h, w.data_ptr(), w.shape[0], out.data_ptr()))
+        return out
 
     def push(self, d):
         """One step of a distribution ``d`` ``[S]`` (the scatter form, ``index_add_``): ``out[succ[s][i]] +=

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define PBN_ABI_VERSION 23
+#define PBN_ABI_VERSION 24
 
 enum {
     PBN_OK = 0,
@@ -608,6 +608,35 @@ int pbn_stg_clear_leaks(pbn_stg *g);
  * above PBN_STG_MAX_CELLS is PBN_E_INVALID. Rows past S: PBN_E_RANGE; a NULL array: PBN_E_INVALID; a host-only
  * handle: PBN_E_STATE; n_rows == 0: nothing is launched. */
 int pbn_stg_rows_device(pbn_stg *g, uint64_t first_row, uint64_t n_rows, void *d_mass, void *d_succ);
+
+/* ---- Exact optimal control over a transition graph (csrc/pbn_control.hip): the per-sweep work of value
+ * iteration for the single-flip MDP of PBNEnv.step + _get_reward (pbn_env.py:125-188) on the arrays above. The
+ * reference trains agents against this MDP and has no code that solves it. An action is the no-op or the flip of one
+ * allowed node; the flip is a map between rows of the set (nbr), the update that follows is the graph's law (mass,
+ * succ). Values are float64; nbr and the action restriction are exact.
+ * All four calls are one launch on the device's default stream, asynchronous, as pbn_stg_rows_device is. A NULL array:
+ * PBN_E_INVALID; a host-only handle: PBN_E_STATE, decided after the argument checks. ---- */
+#define PBN_STG_LOOKUP_MAX ((uint64_t)1 << 32)
+/* Fills d_nbr [n_rows][N] int32 for rows [first_row, first_row + n_rows): the row of x_s ^ (1 << i) whatever the mass of
+ * that flip under the dynamics; -1 where that state is no row, and -1 without a probe for a node whose bit in
+ * action_mask (host [W] words, NULL = every node) is clear. A mask bit past node N-1: PBN_E_INVALID; rows past S:
+ * PBN_E_RANGE; n_rows == 0: nothing is launched. */
+int pbn_stg_flip_rows_device(pbn_stg *g, uint64_t first_row, uint64_t n_rows, const uint64_t *action_mask, void *d_nbr);
+/* The fused pull over all S rows: d_out[s] = v[s] + (sum_i (double)mass[s][i] * (v[succ[s][i]] - v[s])) * 2^-53 /
+ * n_movable, from d_mass [S][N] uint64, d_succ [S][N] int32 (what pbn_stg_rows_device wrote for the whole graph) and
+ * d_v [S]. With d_pen [S] it also writes d_out_pen[s] = d_out[s] - cost * d_pen[s] (d_out_pen NULL then:
+ * PBN_E_INVALID). d_out may not alias d_v. The sum of a row is taken in an order fixed by N alone: the result is
+ * bit-identical from call to call and under any grid. A successor that is no row is read as "stays": the caller
+ * checks that the set is closed (pbn_stg_info.leaks == 0). */
+int pbn_stg_expect_device(pbn_stg *g, const void *d_mass, const void *d_succ, const double *d_v, double *d_out,
+                          const double *d_pen, double cost, double *d_out_pen);
+/* d_v[s] = max(d_u[s], max over nodes i with d_nbr[s][i] >= 0 of d_ua[d_nbr[s][i]]) and d_policy[s] = the arg max: -1
+ * for the no-op, else the node; on a tie the no-op first, then the lowest node. d_v may not alias d_u or d_ua. */
+int pbn_stg_backup_device(pbn_stg *g, const void *d_nbr, const double *d_u, const double *d_ua, double *d_v,
+                          int32_t *d_policy);
+/* d_rows[e] = the row of d_words[e] ([n][W] device words), -1 for a state that is no row: pbn_stateset_lookup_device's
+ * kernel over the graph's own table. n above PBN_STG_LOOKUP_MAX: PBN_E_RANGE; n == 0: nothing is launched. */
+int pbn_stg_lookup_device(pbn_stg *g, const void *d_words, uint64_t n, int32_t *d_rows);
 
 #ifdef __cplusplus
 }
