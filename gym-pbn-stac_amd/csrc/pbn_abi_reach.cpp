@@ -20,10 +20,8 @@ static int reach_create(pbn_net* net, int device, uint64_t max_states, int graph
     // entries lost to publish races are dead until the next level hands them out again: room for one level's
     // worth (measured: up to ~1.3 per new state on a 2^19-state cube), and a floor for small sets
     r->key_cap = r->max_states + r->max_states / 2u + 65536u;
-    r->fcap = 64;
-    while (r->fcap < r->key_cap) r->fcap *= 2u;
-    r->tcap = 64;
-    while (r->tcap < 2ull * r->max_states) r->tcap *= 2u;  // load factor <= 1/2 at max_states
+    r->fcap = keytable_pow2(r->key_cap);
+    r->tcap = keytable_pow2(2ull * r->max_states);  // load factor <= 1/2 at max_states
     auto bail = [&](int code) {
         pbn_reach_destroy(r);
         return code;

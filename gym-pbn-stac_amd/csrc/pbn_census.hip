@@ -73,8 +73,8 @@ __global__ __launch_bounds__(BLOCK) void k_census(CensusArgs a) {
         lane_adds += __shfl_xor(lane_adds, d);
     }
     if ((threadIdx.x & 63u) == 0u) {
-        if (lane_dropped) __hip_atomic_fetch_add(a.dropped, (unsigned long long)lane_dropped, CENSUS_RLX, CENSUS_AGENT);
-        if (lane_adds) __hip_atomic_fetch_add(a.adds, (unsigned long long)lane_adds, CENSUS_RLX, CENSUS_AGENT);
+        if (lane_dropped) __hip_atomic_fetch_add(a.dropped, (unsigned long long)lane_dropped, KEYTABLE_RLX, KEYTABLE_AGENT);
+        if (lane_adds) __hip_atomic_fetch_add(a.adds, (unsigned long long)lane_adds, KEYTABLE_RLX, KEYTABLE_AGENT);
     }
 }
 

@@ -4,10 +4,9 @@
 // pbn_target.py:538-560, pbn_target_multi.py:465-487). Here the dict is a device table: one u64 count per distinct
 // state, found or inserted without any lane waiting for another.
 //
-// Layout (the reach set's, pbn_reach.hip, plus counts):
-//   table  [slots] u64   open addressing, linear probing: 0 = empty, else hash tag << 32 | entry + 1; written once
-//                        (CAS from 0) and never changed until a clear. slots = the power of two >= 2 max_states,
-//                        at least 64.
+// Layout (the table and keys of pbn_keytable.hpp, where the find-or-insert walk and its ordering argument are, plus
+// counts):
+//   table  [slots] u64   slots = the power of two >= 2 max_states, at least 64; unchanged until a clear.
 //   keys   [key_cap][W] u64   entry e's words; key_cap = max_states + CENSUS_SLACK. An entry is LIVE once a slot
 //                        names it, DEAD while it is reserved and unpublished: its inserter lost the publish to an
 //                        equal key or found no slot.
@@ -33,23 +32,23 @@
 // finds every slot taken, the visit is dropped on the device.
 //
 // This part includes no HIP header: sizing, the sample-point rule, a sequential model of the same layout and the
-// compaction run on the host (pbn_abi_census.cpp, tests/host/census_check.cpp). The find-or-insert that kernels
-// run is below the __HIPCC__ guard.
+// compaction run on the host (pbn_abi_census.cpp, tests/host/census_check.cpp). What the kernels run is below the
+// __HIPCC__ guard.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 
 #include <vector>
 
+#include "pbn_keytable.hpp"
 #include "pbn_params.hpp"
 #include "pbn_stateset.hpp"
 
 namespace pbn {
 
 constexpr uint64_t CENSUS_MAX_STATES = STATESET_MAX_STATES;  // 2^24: what a StateSet takes
-constexpr uint32_t CENSUS_MIN_SLOTS = 64;
 constexpr uint32_t CENSUS_MAX_UPDATES = 65536;  // per launch (the TENV_MACRO_MAX_T precedent): a launch stays bounded
-constexpr uint32_t CENSUS_NONE = 0xFFFFFFFFu;
+constexpr uint32_t CENSUS_NONE = KEYTABLE_NONE;
 // entries past max_states, one for every lane of a launch to hold dead: 2,048 workgroups of BLOCK lanes, which is
 // what 256 CUs keep resident at most (8 workgroups of 256 threads each)
 constexpr uint32_t CENSUS_SLACK = 1u << 19;
@@ -69,20 +68,14 @@ enum {
 };
 
 constexpr uint32_t census_slots(uint64_t max_states) {
-    uint64_t s = CENSUS_MIN_SLOTS;
-    while (s < 2 * max_states) s *= 2;
-    return (uint32_t)s;  // max_states <= 2^24: at most 2^25
+    return keytable_pow2(2 * max_states);  // max_states <= 2^24: at most 2^25
 }
 
 constexpr uint32_t census_key_cap(uint64_t max_states, uint32_t slack = CENSUS_SLACK) {
     return (uint32_t)max_states + slack;
 }
 
-constexpr uint32_t census_ring_cap(uint32_t key_cap) {  // a power of two >= key_cap: every entry fits at once
-    uint64_t s = 64;
-    while (s < key_cap) s *= 2;
-    return (uint32_t)s;
-}
+constexpr uint32_t census_ring_cap(uint32_t key_cap) { return keytable_pow2(key_cap); }  // every entry fits at once
 
 // Sample points: "the state after i updates" is counted for i = first, first + stride, ... <= n_updates.
 constexpr uint64_t census_samples(uint32_t n_updates, uint32_t first, uint32_t stride) {
@@ -193,52 +186,28 @@ struct CensusModel {
         if (*spare == CENSUS_NONE) *spare = reserve();
     }
 
-    // Entry of key (W words), inserted if absent; CENSUS_NONE: absent, and no entry or no slot is left. The walk of
-    // census_find, one lane at a time. *spare: the lane's spare entry, as on the device (used first; an entry taken in
-    // vain comes back into it; a walk that takes none leaves it alone). rival: another lane publishes the key between
-    // this lane's look at the empty slot and its CAS, so this lane, entry in hand, loses and adopts.
+    // The census' bookkeeping, as CensusTable has it on the device. spare: the lane's spare entry (used first; an
+    // entry taken in vain comes back into it; a walk that takes none leaves it alone).
+    struct Table {
+        CensusModel& m;
+        uint32_t& spare;
+        uint32_t take() const { return spare != CENSUS_NONE ? std::exchange(spare, CENSUS_NONE) : m.reserve(); }
+        void none() const {}
+        void full() const {}
+        void published(uint32_t mine) const {
+            if (m.ctl[CENSUS_COUNT]++ >= m.max_states) m.counts[mine] |= CENSUS_OVER;
+        }
+        void unused(uint32_t mine) const { spare = mine; }
+    };
+    // Entry of key (W words), inserted if absent; CENSUS_NONE: absent, and no entry or no slot is left: keytable_walk,
+    // one lane at a time. rival: another lane publishes the key between this lane's look at the empty slot and its
+    // CAS (that lane's walk ends at this very slot), so this lane, entry in hand, loses and adopts.
     uint32_t find(const uint64_t* key, uint32_t* spare = nullptr, bool rival = false) {
         uint32_t none = CENSUS_NONE;
         if (!spare) spare = &none;  // a lane of its own without a spare
-        const uint64_t h = stateset_by_words(W, [&](auto w) -> uint64_t {
-            constexpr int WW = decltype(w)::value;
-            uint64_t s[WW];
-            for (int k = 0; k < WW; ++k) s[k] = key[k];
-            return stateset_hash<WW>(s);
-        });
-        const uint32_t tag = (uint32_t)(h >> 32);
-        uint32_t slot = (uint32_t)h & tmask, mine = CENSUS_NONE;
-        for (uint32_t probe = 0; probe <= tmask; ++probe, slot = (slot + 1u) & tmask) {
-            uint64_t v = table[slot];
-            if (v == 0) {
-                if (mine == CENSUS_NONE) {
-                    mine = *spare != CENSUS_NONE ? *spare : reserve();
-                    *spare = CENSUS_NONE;
-                    if (mine == CENSUS_NONE) return CENSUS_NONE;
-                    for (int k = 0; k < W; ++k) keys[(size_t)mine * W + k] = key[k];
-                }
-                if (rival) {
-                    rival = false;
-                    (void)find(key);  // the other lane's walk ends at this very slot
-                    v = table[slot];
-                }
-                if (v == 0) {
-                    table[slot] = ((uint64_t)tag << 32) | (uint64_t)(mine + 1u);
-                    if (ctl[CENSUS_COUNT]++ >= max_states) counts[mine] |= CENSUS_OVER;
-                    return mine;
-                }
-            }
-            if ((uint32_t)(v >> 32) != tag) continue;
-            const uint32_t j = (uint32_t)v - 1u;
-            bool same = true;
-            for (int k = 0; k < W; ++k) same = same && keys[(size_t)j * W + k] == key[k];
-            if (same) {
-                if (mine != CENSUS_NONE) *spare = mine;
-                return j;
-            }
-        }
-        if (mine != CENSUS_NONE) *spare = mine;
-        return CENSUS_NONE;
+        KeytableHostMem mem{table, keys, nullptr};
+        if (rival) mem.rival = [this, key] { (void)find(key); };
+        return keytable_find_host<true>(W, mem, Table{*this, *spare}, tmask, key);
     }
     void visit(const uint64_t* key, uint64_t n = 1, uint32_t* spare = nullptr, bool rival = false) {
         visits += n;
@@ -261,16 +230,6 @@ struct CensusModel {
 #if defined(__HIPCC__)
 namespace pbn {
 
-// Words another lane may read or write within the same launch go through agent-scope atomics on both sides (the
-// per-XCD L2s are not coherent with each other, an L1 is not refreshed by other CUs' stores): pbn_reach.hip.
-#define CENSUS_RLX __ATOMIC_RELAXED
-#define CENSUS_AGENT __HIP_MEMORY_SCOPE_AGENT
-
-__device__ __forceinline__ unsigned long long census_ld64(const unsigned long long* p) {
-    return __hip_atomic_load(p, CENSUS_RLX, CENSUS_AGENT);
-}
-__device__ __forceinline__ uint32_t census_ld32(const uint32_t* p) { return __hip_atomic_load(p, CENSUS_RLX, CENSUS_AGENT); }
-
 // An entry nobody else knows of, or CENSUS_NONE. No loop: at most one add (and one add back) on the ring's head, one
 // add on the key array. The ring taken from is not pushed onto in this launch, so its tail is fixed and a position
 // below it holds an entry an earlier launch wrote. A lane draws a position with fetch_add; a position at or past the
@@ -282,14 +241,14 @@ __device__ __forceinline__ uint32_t census_ld32(const uint32_t* p) { return __hi
 // key_cap by at most the lanes in flight.
 __device__ __forceinline__ uint32_t census_reserve(const CensusArgs& a) {
     const uint32_t t = a.parity ^ 1u;
-    const uint32_t tail = census_ld32(a.ctl + CENSUS_TAIL0 + t);
-    if ((int32_t)(tail - census_ld32(a.ctl + CENSUS_HEAD0 + t)) > 0) {
-        const uint32_t h = __hip_atomic_fetch_add(a.ctl + CENSUS_HEAD0 + t, 1u, CENSUS_RLX, CENSUS_AGENT);
-        if ((int32_t)(tail - h) > 0) return census_ld32(a.ring + (size_t)t * (a.ring_mask + 1u) + (h & a.ring_mask));
-        __hip_atomic_fetch_sub(a.ctl + CENSUS_HEAD0 + t, 1u, CENSUS_RLX, CENSUS_AGENT);
+    const uint32_t tail = keytable_ld32(a.ctl + CENSUS_TAIL0 + t);
+    if ((int32_t)(tail - keytable_ld32(a.ctl + CENSUS_HEAD0 + t)) > 0) {
+        const uint32_t h = __hip_atomic_fetch_add(a.ctl + CENSUS_HEAD0 + t, 1u, KEYTABLE_RLX, KEYTABLE_AGENT);
+        if ((int32_t)(tail - h) > 0) return keytable_ld32(a.ring + (size_t)t * (a.ring_mask + 1u) + (h & a.ring_mask));
+        __hip_atomic_fetch_sub(a.ctl + CENSUS_HEAD0 + t, 1u, KEYTABLE_RLX, KEYTABLE_AGENT);
     }
-    if (census_ld32(a.ctl + CENSUS_KEYS) < a.key_cap) {
-        const uint32_t e = __hip_atomic_fetch_add(a.ctl + CENSUS_KEYS, 1u, CENSUS_RLX, CENSUS_AGENT);
+    if (keytable_ld32(a.ctl + CENSUS_KEYS) < a.key_cap) {
+        const uint32_t e = __hip_atomic_fetch_add(a.ctl + CENSUS_KEYS, 1u, KEYTABLE_RLX, KEYTABLE_AGENT);
         if (e < a.key_cap) return e;
     }
     return CENSUS_NONE;
@@ -297,80 +256,39 @@ __device__ __forceinline__ uint32_t census_reserve(const CensusArgs& a) {
 
 // A lane's spare at the end of its work: onto this launch's ring, for later launches (its count is 0 and stays 0).
 __device__ __forceinline__ void census_retire(const CensusArgs& a, uint32_t e) {
-    const uint32_t p = __hip_atomic_fetch_add(a.ctl + CENSUS_TAIL0 + a.parity, 1u, CENSUS_RLX, CENSUS_AGENT);
+    const uint32_t p = __hip_atomic_fetch_add(a.ctl + CENSUS_TAIL0 + a.parity, 1u, KEYTABLE_RLX, KEYTABLE_AGENT);
     a.ring[(size_t)a.parity * (a.ring_mask + 1u) + (p & a.ring_mask)] = e;  // read by later launches only
 }
 
+// The census' bookkeeping for keytable_walk. `spare`: the lane's dead entry from an earlier call, used first and handed
+// back if this call takes an entry it does not publish (a walk that meets no empty slot -- the common case, a key
+// already held -- takes none and leaves the spare as it was). Nothing is flagged when no entry or no slot is left: the
+// caller counts the visit as dropped.
+struct CensusTable {
+    const CensusArgs& a;
+    uint32_t& spare;
+    __device__ __forceinline__ uint32_t take() const {
+        const uint32_t mine = spare != CENSUS_NONE ? spare : census_reserve(a);
+        spare = CENSUS_NONE;
+        return mine;
+    }
+    __device__ __forceinline__ void none() const {}
+    __device__ __forceinline__ void full() const {}
+    // the rank: past max_states the entry is kept (so that nobody inserts the state again) but marked, and the
+    // read-out counts its visits as dropped
+    __device__ __forceinline__ void published(uint32_t mine) const {
+        if (KeytableDeviceCtl::add(a.ctl + CENSUS_COUNT) >= a.max_states)
+            __hip_atomic_fetch_or(a.counts + mine, (unsigned long long)CENSUS_OVER, KEYTABLE_RLX, KEYTABLE_AGENT);
+    }
+    __device__ __forceinline__ void unused(uint32_t mine) const { spare = mine; }
+};
+
 // Entry index of key s, inserted if absent; CENSUS_NONE: absent and not insertable -- no entry is left, or every
-// slot of the walk holds another key. `spare`: the lane's dead entry from an earlier call, used first and handed back
-// if this call takes an entry it does not publish.
-//
-// The protocol is reach_find's: an inserter that reaches an empty slot takes an entry, writes its words with
-// agent-scope stores, waits for them and publishes with one CAS of the slot from 0. A loser reads the winner's slot
-// word: same tag and same words -> the key is present and the loser adopts the winner's entry; otherwise it probes on
-// with its entry in hand. A slot never changes once written, so a walk only moves forward and ends after at most
-// tmask + 1 slots. No lane waits for another; every loop is bounded.
+// slot of the walk holds another key.
 template <int W>
 __device__ uint32_t census_find(const CensusArgs& a, const uint64_t (&s)[W], uint32_t& spare) {
-    const uint64_t h = stateset_hash<W>(s);
-    const uint32_t tag = (uint32_t)(h >> 32);
-    uint32_t slot = (uint32_t)h & a.tmask, mine = CENSUS_NONE;
-    for (uint32_t probe = 0; probe <= a.tmask; ++probe, slot = (slot + 1u) & a.tmask) {
-        unsigned long long v = census_ld64(a.table + slot);
-        if (v == 0) {
-            if (mine == CENSUS_NONE) {
-                mine = spare != CENSUS_NONE ? spare : census_reserve(a);
-                spare = CENSUS_NONE;
-                if (mine == CENSUS_NONE) {
-                    // nothing to insert with. The last entry may have gone to this very key a moment ago: look at
-                    // the slot again before calling the visit dropped. What remains: a publish of this key that
-                    // lands after this second look is missed, and the visit is dropped although the state is in
-                    // the table -- the reported count is then below the true one, never above.
-                    v = census_ld64(a.table + slot);
-                    if (v == 0) return CENSUS_NONE;
-                } else {
-                    unsigned long long* kw = reinterpret_cast<unsigned long long*>(a.keys) + (uint64_t)mine * W;
-#pragma unroll
-                    for (int k = 0; k < W; ++k)
-                        __hip_atomic_store(kw + k, (unsigned long long)s[k], CENSUS_RLX, CENSUS_AGENT);
-                    // Publish order without a release fence (pbn_reach.hip): the key words are agent-scope atomic
-                    // stores, written through past this XCD's L2, and vmcnt(0) holds the wave until they are
-                    // acknowledged; only then is the CAS issued. A reader takes the entry index out of the slot
-                    // word it loaded, so its key loads (agent-scope, past L1) cannot be issued before that load
-                    // has returned.
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                }
-            }
-            if (v == 0) {
-                unsigned long long expect = 0;
-                const unsigned long long want = ((unsigned long long)tag << 32) | (unsigned long long)(mine + 1u);
-                if (__hip_atomic_compare_exchange_strong(a.table + slot, &expect, want, CENSUS_RLX, CENSUS_RLX,
-                                                         CENSUS_AGENT)) {
-                    // the rank: past max_states the entry is kept (so that nobody inserts the state again) but
-                    // marked, and the read-out counts its visits as dropped
-                    if (__hip_atomic_fetch_add(a.ctl + CENSUS_COUNT, 1u, CENSUS_RLX, CENSUS_AGENT) >= a.max_states)
-                        __hip_atomic_fetch_or(a.counts + mine, (unsigned long long)CENSUS_OVER, CENSUS_RLX, CENSUS_AGENT);
-                    return mine;
-                }
-                v = expect;
-            }
-        }
-        if ((uint32_t)(v >> 32) == tag) {
-            const uint32_t j = (uint32_t)v - 1u;
-            const unsigned long long* kw = reinterpret_cast<const unsigned long long*>(a.keys) + (uint64_t)j * W;
-            bool same = true;
-#pragma unroll
-            for (int k = 0; k < W; ++k) same &= census_ld64(kw + k) == (unsigned long long)s[k];
-            if (same) {
-                // an entry this call took in vain is the lane's spare again. mine is CENSUS_NONE when the walk met
-                // no empty slot -- the common case, a key already held -- and the spare then stays as it was
-                if (mine != CENSUS_NONE) spare = mine;
-                return j;
-            }
-        }
-    }
-    if (mine != CENSUS_NONE) spare = mine;  // every slot taken by other keys
-    return CENSUS_NONE;
+    return keytable_walk<W, true>(KeytableDeviceMem{a.table, reinterpret_cast<unsigned long long*>(a.keys)},
+                                  CensusTable{a, spare}, a.tmask, s);
 }
 
 // A lane's pending run: the entry of the last counted key and how many visits of it are not in memory yet.
@@ -386,7 +304,7 @@ template <int W>
 __device__ __forceinline__ void census_flush(const CensusArgs& a, CensusRun<W>& r, uint64_t& dropped, uint64_t& adds) {
     if (r.pending == 0u) return;
     const bool held = r.entry != CENSUS_NONE;
-    if (held) __hip_atomic_fetch_add(a.counts + r.entry, (unsigned long long)r.pending, CENSUS_RLX, CENSUS_AGENT);
+    if (held) __hip_atomic_fetch_add(a.counts + r.entry, (unsigned long long)r.pending, KEYTABLE_RLX, KEYTABLE_AGENT);
     // both tallies move by a select, outside the branch: with one 64-bit tally bumped on each side of it the compiler
     // picks the tally by address and keeps the two in scratch
     adds += held ? 1u : 0u;

@@ -17,24 +17,14 @@
 // The set is wait-free: no lane ever waits for another lane's progress. Every loop is bounded by the table
 // size, and a full table / key array / max_states only raises the overflow word.
 #include "pbn_device.hpp"
+#include "pbn_keytable.hpp"
+#include "pbn_lane_env.hpp"
 #include "pbn_launch.hpp"
 #include "pbn_reach_rule.hpp"
 
 namespace pbn {
 
 namespace {
-
-// Words another wave may read within the same launch go through 8-byte (4-byte for counters and marks)
-// agent-scope atomics on both sides: per-XCD L2s are not coherent and an L1 is not refreshed by other
-// CUs' stores.
-#define RLX __ATOMIC_RELAXED
-#define AGENT __HIP_MEMORY_SCOPE_AGENT
-
-__device__ __forceinline__ unsigned long long ld64(const unsigned long long* p) {
-    return __hip_atomic_load(p, RLX, AGENT);
-}
-__device__ __forceinline__ uint32_t ld32(const uint32_t* p) { return __hip_atomic_load(p, RLX, AGENT); }
-__device__ __forceinline__ void raise_flag(uint32_t* p) { __hip_atomic_store(p, 1u, RLX, AGENT); }
 
 // 1 iff node i can flip at state s (pbn_reach_rule.hpp), the state words read out of registers.
 template <int W, int KIND>
@@ -43,113 +33,14 @@ __device__ __forceinline__ uint32_t can_flip_at(const uint64_t (&s)[W], uint32_t
     return can_flip<KIND>([&](uint32_t j) { return getbit<W>(s, j); }, i, a.first_node, tbl, a.L);
 }
 
-template <int W>
-__device__ __forceinline__ void flip_bit(uint64_t (&s)[W], uint32_t i) {
-    const uint64_t bit = (uint64_t)1 << (i & 63u);
-    const uint32_t wi = i >> 6;
-#pragma unroll
-    for (int k = 0; k < W; ++k) s[k] ^= bit & (uint64_t)(int64_t)(int32_t)lane_mask(wi, (uint32_t)k);
-}
-
-template <int W>
-__device__ __forceinline__ uint64_t reach_hash(const uint64_t (&s)[W]) {
-    uint64_t h = 0x9E3779B97F4A7C15ull;
-#pragma unroll
-    for (int k = 0; k < W; ++k) {
-        h = (h ^ s[k]) * 0xFF51AFD7ED558CCDull;
-        h ^= h >> 33;
-    }
-    h *= 0xC4CEB9FE1A85EC53ull;
-    return h ^ (h >> 29);
-}
-
-// Entry index of state s, or REACH_NONE. INSERT: add it if absent (REACH_NONE then means overflow).
-// Protocol: an inserter that reaches an empty slot reserves an entry (from the free ring, else an atomic add
-// on the key array), writes its words with write-through stores, waits for them, and publishes with one CAS
-// of the slot from 0; the publisher appends the entry to the queue (the next frontier). A loser reads the
-// winner's slot: same tag and same words -> the state is present and the loser's entry is dead (flagged,
-// pushed onto the free ring for later levels); otherwise it probes on with its entry in hand. A slot never
-// changes once written, so a probe sequence only moves forward and ends after at most tmask + 1 slots.
-__device__ __forceinline__ void reach_drop(const ReachArgs& a, uint32_t e) {
-    a.mark[e] = REACH_DEAD;  // marks and ring entries are read by later launches only
-    a.free_ring[__hip_atomic_fetch_add(a.ctl + REACH_FREE_TAIL, 1u, RLX, AGENT) & a.fmask] = e;
-}
-
+// Entry index of state s, or REACH_NONE. INSERT: add it if absent (REACH_NONE then means overflow). The walk and its
+// protocol are keytable_walk's (pbn_keytable.hpp); what is the reach set's own -- an entry comes from the free ring,
+// else from the end of keys; a publish is counted and appended to the queue (the next frontier); an entry that was not
+// published is marked dead and pushed onto the free ring; no entry or no slot raises the overflow word -- is ReachTable.
 template <int W, bool INSERT>
 __device__ uint32_t reach_find(const ReachArgs& a, const uint64_t (&s)[W]) {
-    const uint64_t h = reach_hash<W>(s);
-    const uint32_t tag = (uint32_t)(h >> 32);
-    uint32_t slot = (uint32_t)h & a.tmask, mine = REACH_NONE;
-    for (uint32_t probe = 0; probe <= a.tmask; ++probe, slot = (slot + 1u) & a.tmask) {
-        unsigned long long v = ld64(a.table + slot);
-        if (v == 0) {
-            if constexpr (!INSERT) return REACH_NONE;
-            if (mine == REACH_NONE) {
-                if (ld32(a.ctl + REACH_COUNT) >= a.max_states) {
-                    // the count may have just been raised by this very state's publish: look again, after the
-                    // count, before calling it an overflow. Order: the publisher adds to the count only once
-                    // its CAS has returned (the add is behind a branch on the CAS result), and this second
-                    // slot load is issued only once the count's value is here (it is behind a branch on it);
-                    // both words are served at agent scope. Were the order ever lost, the outcome is a
-                    // spurious complete = 0, never a wrong set.
-                    v = ld64(a.table + slot);
-                    if (v == 0) {
-                        raise_flag(a.ctl + REACH_OVERFLOW);
-                        return REACH_NONE;
-                    }
-                } else {
-                    if (a.free_any) {
-                        const uint32_t q = __hip_atomic_fetch_add(a.ctl + REACH_FREE_HEAD, 1u, RLX, AGENT);
-                        if ((int32_t)(a.free_limit - q) > 0) mine = a.free_ring[q & a.fmask];
-                    }
-                    if (mine == REACH_NONE) mine = __hip_atomic_fetch_add(a.ctl + REACH_KEYS, 1u, RLX, AGENT);
-                    if (mine >= a.key_cap) {  // nothing of this entry exists: nothing to drop
-                        raise_flag(a.ctl + REACH_OVERFLOW);
-                        return REACH_NONE;
-                    }
-                    unsigned long long* kw = reinterpret_cast<unsigned long long*>(a.keys) + (uint64_t)mine * W;
-#pragma unroll
-                    for (int k = 0; k < W; ++k) __hip_atomic_store(kw + k, (unsigned long long)s[k], RLX, AGENT);
-                    a.mark[mine] = 0;  // read by later launches only
-                    // Publish order without a release fence (an agent-scope release writes back the whole
-                    // L2, ~1.7 us per insert): the key words above are agent-scope atomic stores, i.e.
-                    // write-through past this XCD's L2, and vmcnt(0) holds the wave until they are
-                    // acknowledged -- only then is the CAS below issued. The "memory" clobber keeps the
-                    // compiler from moving either side across it. A reader takes the entry index out of the
-                    // slot word it loaded, so its key loads (agent-scope atomic loads, which bypass L1)
-                    // cannot be issued before that slot load has returned.
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                }
-            }
-            if (v == 0) {
-                unsigned long long expect = 0;
-                const unsigned long long want = ((unsigned long long)tag << 32) | (unsigned long long)(mine + 1u);
-                if (__hip_atomic_compare_exchange_strong(a.table + slot, &expect, want, RLX, RLX, AGENT)) {
-                    __hip_atomic_fetch_add(a.ctl + REACH_COUNT, 1u, RLX, AGENT);
-                    const uint32_t p = __hip_atomic_fetch_add(a.ctl + REACH_QTAIL, 1u, RLX, AGENT);
-                    if (p < a.key_cap) a.queue[p] = mine;  // one append per live entry: p < key_cap
-                    return mine;
-                }
-                v = expect;
-            }
-        }
-        if ((uint32_t)(v >> 32) == tag) {
-            const uint32_t j = (uint32_t)v - 1u;
-            const unsigned long long* kw = reinterpret_cast<const unsigned long long*>(a.keys) + (uint64_t)j * W;
-            bool same = true;
-#pragma unroll
-            for (int k = 0; k < W; ++k) same &= ld64(kw + k) == (unsigned long long)s[k];
-            if (same) {
-                if (mine != REACH_NONE) reach_drop(a, mine);
-                return j;
-            }
-        }
-    }
-    if constexpr (INSERT) {  // every slot taken by other states
-        raise_flag(a.ctl + REACH_OVERFLOW);
-        if (mine != REACH_NONE) reach_drop(a, mine);
-    }
-    return REACH_NONE;
+    return keytable_walk<W, INSERT>(KeytableDeviceMem{a.table, reinterpret_cast<unsigned long long*>(a.keys)},
+                                    ReachTable<KeytableDeviceCtl>{a}, a.tmask, s);
 }
 
 __device__ __forceinline__ const uint8_t* stage(const ReachArgs& a, uint8_t* lds) {
@@ -206,7 +97,7 @@ __global__ __launch_bounds__(BLOCK) void k_reach_expand(ReachArgs a) {
             uint64_t t[W];
 #pragma unroll
             for (int k = 0; k < W; ++k) t[k] = s[k];
-            flip_bit<W>(t, i);
+            xor_bit<W>(t, i, true);
             (void)reach_find<W, true>(a, t);
         }
     }
@@ -221,7 +112,7 @@ __global__ __launch_bounds__(64) void k_reach_back_start(ReachArgs a) {
     for (int k = 0; k < W; ++k) s[k] = a.in[k];
     const uint32_t j = reach_find<W, false>(a, s);
     if (j == REACH_NONE) {
-        raise_flag(a.ctl + REACH_MISSING);
+        KeytableDeviceCtl::raise(a.ctl + REACH_MISSING);
         return;
     }
     a.mark[j] = a.epoch;
@@ -247,12 +138,12 @@ __global__ __launch_bounds__(BLOCK) void k_reach_back(ReachArgs a) {
             uint64_t x[W];
 #pragma unroll
             for (int k = 0; k < W; ++k) x[k] = s[k];
-            flip_bit<W>(x, i);
+            xor_bit<W>(x, i, true);
             const uint32_t j = reach_find<W, false>(a, x);
-            if (j == REACH_NONE || ld32(a.mark + j) == a.epoch) continue;
+            if (j == REACH_NONE || keytable_ld32(a.mark + j) == a.epoch) continue;
             if (!can_flip_at<W, KIND>(x, i, tbl, a)) continue;
-            if (__hip_atomic_exchange(a.mark + j, a.epoch, RLX, AGENT) != a.epoch) {
-                const uint32_t p = __hip_atomic_fetch_add(a.ctl + REACH_QTAIL, 1u, RLX, AGENT);
+            if (__hip_atomic_exchange(a.mark + j, a.epoch, KEYTABLE_RLX, KEYTABLE_AGENT) != a.epoch) {
+                const uint32_t p = KeytableDeviceCtl::add(a.ctl + REACH_QTAIL);
                 if (p < a.key_cap) a.queue[p] = j;  // one append per entry: p < live entries <= key_cap
             }
         }
@@ -285,8 +176,8 @@ __global__ __launch_bounds__(BLOCK) void k_reach_hull(ReachArgs a) {
             any[k] |= __shfl_xor(any[k], d);
         }
         if ((threadIdx.x & 63u) == 0) {
-            __hip_atomic_fetch_and(a.hull + k, (unsigned long long)all[k], RLX, AGENT);
-            __hip_atomic_fetch_or(a.hull + W + k, (unsigned long long)any[k], RLX, AGENT);
+            __hip_atomic_fetch_and(a.hull + k, (unsigned long long)all[k], KEYTABLE_RLX, KEYTABLE_AGENT);
+            __hip_atomic_fetch_or(a.hull + W + k, (unsigned long long)any[k], KEYTABLE_RLX, KEYTABLE_AGENT);
         }
     }
 }

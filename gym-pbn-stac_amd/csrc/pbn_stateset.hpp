@@ -15,42 +15,17 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include <type_traits>
 #include <vector>
 
-#ifndef PBN_HD  // as in pbn_reach_rule.hpp
-#if defined(__HIPCC__)  // the compiler's own attributes: no HIP header needed for them
-#define PBN_HD __attribute__((host)) __attribute__((device)) inline __attribute__((always_inline))
-#else
-#define PBN_HD inline
-#endif
-#endif
+#include "pbn_keytable.hpp"  // PBN_HD, stateset_hash, keytable_pow2, stateset_by_words
 
 namespace pbn {
 
 constexpr uint64_t STATESET_MAX_STATES = 1ull << 24;  // 2^25 slots: 128 MiB of meta + 256 MiB of keys at W = 1
-constexpr uint32_t STATESET_MIN_SLOTS = 64;
 constexpr int STATESET_MAX_WORDS = 8;
 
-// The mixing of reach_hash (pbn_reach.hip, which keeps its own copy).
-template <int W>
-PBN_HD uint64_t stateset_hash(const uint64_t (&s)[W]) {
-    uint64_t h = 0x9E3779B97F4A7C15ull;
-#if defined(__HIPCC__)
-#pragma unroll
-#endif
-    for (int k = 0; k < W; ++k) {
-        h = (h ^ s[k]) * 0xFF51AFD7ED558CCDull;
-        h ^= h >> 33;
-    }
-    h *= 0xC4CEB9FE1A85EC53ull;
-    return h ^ (h >> 29);
-}
-
 constexpr uint32_t stateset_slots(uint64_t n_states) {
-    uint64_t s = STATESET_MIN_SLOTS;
-    while (s < 2 * n_states) s *= 2;
-    return (uint32_t)s;  // n_states <= 2^24: at most 2^25
+    return keytable_pow2(2 * n_states);  // n_states <= 2^24: at most 2^25
 }
 
 // Label of state s, or -1. The walk starts at the state's home slot and ends at an empty slot, at the member,
@@ -79,21 +54,6 @@ PBN_HD int32_t stateset_lookup(const uint64_t (&s)[W], const uint32_t* meta, con
         if (diff == 0) return (int32_t)(m - 1u);
     }
     return -1;
-}
-
-// Run-time words per state -> compile-time (host side; the kernels' dispatch is by_words, pbn_launch.hpp).
-template <class F>
-inline auto stateset_by_words(int W, F&& f) {
-    switch (W) {
-        case 1: return f(std::integral_constant<int, 1>{});
-        case 2: return f(std::integral_constant<int, 2>{});
-        case 3: return f(std::integral_constant<int, 3>{});
-        case 4: return f(std::integral_constant<int, 4>{});
-        case 5: return f(std::integral_constant<int, 5>{});
-        case 6: return f(std::integral_constant<int, 6>{});
-        case 7: return f(std::integral_constant<int, 7>{});
-        default: return f(std::integral_constant<int, 8>{});
-    }
 }
 
 // The host copy of a set: what the builder makes, the host lookup reads and the upload copies.

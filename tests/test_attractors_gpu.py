@@ -138,8 +138,9 @@ def test_per_seed_path_merges_seeds_of_one_attractor():
 
 
 # ---------------------------------------------------------------- W = 4 closure
-def test_closure_four_words_matches_embedded_network():
-    from gym_pbn_amd.attractors import ReachSet, sort_rows
+def four_word_embedding():
+    """bittner28, its embedding into 199 nodes with live nodes in all four words, the positions, and a state of
+    bittner28 after a long rollout."""
     from gym_pbn_amd.batch import PBNBatch
     from gym_pbn_amd.network import load_network
 
@@ -151,7 +152,13 @@ def test_closure_four_words_matches_embedded_network():
     b = PBNBatch(small, 1, seed=4)
     b.randomize()
     b.rollout(64 * 28)
-    seed = b.get_state()
+    return small, big, place, b.get_state()
+
+
+def test_closure_four_words_matches_embedded_network():
+    from gym_pbn_amd.attractors import ReachSet, sort_rows
+
+    small, big, place, seed = four_word_embedding()
     rs = ReachSet(small, 1 << 17)
     n, complete = rs.closure(seed)
     assert complete and n >= 2
@@ -164,6 +171,35 @@ def test_closure_four_words_matches_embedded_network():
     a, o = rb.hull()
     assert np.array_equal(a, np.bitwise_and.reduce(rb.read()[0], axis=0))
     assert np.array_equal(o, np.bitwise_or.reduce(rb.read()[0], axis=0))
+
+
+@pytest.mark.parametrize("n_words", [1, 4])
+def test_closure_of_repeated_seeds_is_the_closure_of_the_distinct_ones(n_words):
+    """3 distinct seed states, each 4,096 times, shuffled: 12,288 lanes in 48 workgroups race for 3 keys. All but 3
+    lose their publish, adopt the winner's entry and drop their own, and the expand levels take the dropped entries
+    off the free ring. The set must be the one the 3 seeds alone give. W = 4: the same seed of the embedded network
+    under three settings of two frozen nodes -- three disjoint copies of one closure."""
+    from gym_pbn_amd.attractors import ReachSet, sort_rows
+
+    if n_words == 1:
+        net, cap = case_network(case_by(10, 2, 4)), SMALL
+        seeds = np.array([[3], [100], [517]], np.uint64)
+    else:
+        _, net, place, seed = four_word_embedding()
+        cap = 3 << 17  # three times what one copy's closure fits (the test above)
+        frozen = np.random.default_rng(12).integers(0, 2, size=(3, 199), dtype=np.uint8)
+        free = np.setdiff1d(np.arange(199), place)[:2]
+        frozen[:, free] = [[0, 0], [0, 1], [1, 0]]
+        seeds = np.concatenate([lift_states(seed, 28, 199, place, f) for f in frozen])
+    assert seeds.shape == (3, n_words) and len(np.unique(seeds, axis=0)) == 3
+    rs = ReachSet(net, cap)
+    count, complete = rs.closure(seeds)
+    assert complete and count >= 3
+    want = sort_rows(rs.read()[0])
+    many = np.repeat(seeds, 4096, axis=0)
+    np.random.default_rng(7).shuffle(many, axis=0)
+    assert rs.closure(many) == (count, complete)
+    assert np.array_equal(sort_rows(rs.read()[0]), want)
 
 
 # ---------------------------------------------------------------- capacity
