@@ -64,6 +64,8 @@ struct GroupLane {
 // a row: each lane adds its cells j, j + G, ... in that order, then the fixed butterfly over the group's G lanes (the
 // two sides of an exchange add the same two doubles, so every lane ends with the same bits): a function of (N, G).
 // A successor that is no row (a leak: the callers refuse a set that is not closed) is read as "stays".
+// The loop's `acc += m * (...)` compiles to a fused multiply-add under hipcc's default contraction; k_stg_absorb
+// (pbn_absorb.hip) spells that out and a test holds the two bit-equal: mind it when changing the floating-point flags.
 template <int G>
 __global__ __launch_bounds__(BLOCK) void k_stg_expect(StgExpectArgs a) {
     const GroupLane<G> g;

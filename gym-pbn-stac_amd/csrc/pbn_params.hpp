@@ -503,8 +503,27 @@ struct StgBackupArgs {
     uint32_t n_nodes;
 };
 
+// Absorption over a transition graph (pbn_absorb.hip): one Jacobi sweep of n_cols columns of x into out.
+constexpr int STG_ABSORB_MAX_COLS = 8;  // PBN_STG_ABSORB_MAX_COLS
+struct StgAbsorbSrc {
+    double b[STG_ABSORB_MAX_COLS];  // the source constant of each column (the first n_cols are read)
+};
+struct StgAbsorbArgs {
+    const unsigned long long* mass;  // [S][N]
+    const int32_t* succ;             // [S][N]
+    const int32_t* label;            // [S]: -1 a transient row, >= 0 a held row
+    const double* x;                 // [S][ld]
+    double* out;                     // [S][ld], not x: columns [0, n_cols) are written
+    uint64_t ld;                     // >= n_cols
+    uint64_t n_states;
+    uint32_t n_nodes;
+    uint32_t n_cols;                 // [1, STG_ABSORB_MAX_COLS]
+    double n_movable;
+    StgAbsorbSrc src;
+};
+
 // Launchers (pbn_step.hip, pbn_state.hip, pbn_env.hip, pbn_group.hip, pbn_mt.hip, pbn_ssd.hip, pbn_sync.hip, pbn_reach.hip,
-// pbn_tenv.hip, pbn_tenv_macro.hip, pbn_env_set.hip, pbn_stg.hip, pbn_control.hip). Return hipError_t as int.
+// pbn_tenv.hip, pbn_tenv_macro.hip, pbn_env_set.hip, pbn_stg.hip, pbn_control.hip, pbn_absorb.hip). Return hipError_t as int.
 // The lane-per-env kernels (pbn_lane_env.hpp): each file picks its kernel (nullptr: none for that shape), one
 // launcher and one occupancy query serve them all. plane_off: the LDS byte offset of the kernel's state planes;
 // args: the kernel's argument struct.
@@ -527,6 +546,9 @@ void* stg_expect_kernel(uint32_t G, bool one_cell);
 void* stg_backup_kernel(uint32_t G, bool one_cell);
 int launch_control(void* kernel, int grid, void* stream, void* args);
 int max_blocks_control(void* kernel, int* blocks_per_cu);
+// pbn_absorb.hip: the kernel for AbsorbPlan's G, cells_per_lane == 1 and col_tile (nullptr: none for that shape); launched
+// and asked for occupancy through launch_control / max_blocks_control
+void* stg_absorb_kernel(uint32_t G, bool one_cell, uint32_t col_tile);
 int launch_bump(uint64_t* p, uint64_t k, void* stream);
 int launch_set_counters(uint64_t* p, uint64_t v, uint32_t n, void* stream);
 int launch_step(int W, const StepArgs& a, int store_mode, int replay, int sb, int grid, void* stream);

@@ -51,6 +51,10 @@ def __getattr__(name):
         from . import control
 
         return getattr(control, name)
+    if name in ("Absorption", "AbsorptionResult", "host_absorb_sweep"):
+        from . import absorption
+
+        return getattr(absorption, name)
     if name in ("TorchVecPBNEnv", "TorchVecPBNTargetMultiEnv", "TorchVecPBNTargetMultiSetEnv"):
         from . import torch_env
 

@@ -128,6 +128,7 @@ class StgInfo(C.Structure):
 
 STG_MAX_STATES = 1 << 24        # PBN_STG_MAX_STATES
 STG_MAX_CELLS = 1 << 31         # PBN_STG_MAX_CELLS: n_rows * n_nodes of one pbn_stg_rows_device call
+STG_ABSORB_MAX_COLS = 8         # PBN_STG_ABSORB_MAX_COLS: columns of one pbn_stg_absorb_device call
 
 # pbn_tenv_macro_device: modes (PBN_MACRO_*) and the cap on t_max (PBN_TENV_MACRO_MAX_T)
 from .macro_env import MACRO_INTERVAL, MACRO_TRIGGER, TENV_MACRO_MAX_T  # noqa: E402,F401
@@ -228,6 +229,7 @@ SIGNATURES = {
     "pbn_stg_expect_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_double, _vp]),
     "pbn_stg_backup_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "pbn_stg_lookup_device": (C.c_int, [_vp, _vp, C.c_uint64, _vp]),
+    "pbn_stg_absorb_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint64, C.POINTER(C.c_double)]),
 }
 
 

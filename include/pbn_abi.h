@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define PBN_ABI_VERSION 24
+#define PBN_ABI_VERSION 25
 
 enum {
     PBN_OK = 0,
@@ -637,6 +637,28 @@ int pbn_stg_backup_device(pbn_stg *g, const void *d_nbr, const double *d_u, cons
 /* d_rows[e] = the row of d_words[e] ([n][W] device words), -1 for a state that is no row: pbn_stateset_lookup_device's
  * kernel over the graph's own table. n above PBN_STG_LOOKUP_MAX: PBN_E_RANGE; n == 0: nothing is launched. */
 int pbn_stg_lookup_device(pbn_stg *g, const void *d_words, uint64_t n, int32_t *d_rows);
+
+/* ---- Absorption over a transition graph (csrc/pbn_absorb.hip): one Jacobi sweep of the first-hit
+ * recursion over the arrays above, for n_cols columns at once. d_label [S] int32: -1 a transient row, k >= 0 a row of
+ * class k (any labelled row is held: the classes are first-hit classes and need not be closed). For column c of row s,
+ * with d_x and d_out [S][ld] float64, row-major:
+ *   d_out[s][c] = d_x[s][c]                                                          where d_label[s] >= 0 (the same bits)
+ *   d_out[s][c] = (d_x[s][c] + (sum_i (double)mass[s][i] * (d_x[t_i][c] - d_x[s][c])) * 2^-53 / n_movable) + src[c]
+ *                 elsewhere, t_i = succ[s][i]; a successor that is no row is read as "stays", as in
+ *                 pbn_stg_expect_device.
+ * n sweeps from 1{label == k} with src 0 give P(first labelled row is hit within n updates, in class k); from
+ * 1{label < 0} with src 0, P(no labelled row within n updates); from 0 with src 1, E[min(hitting time, n)]: the law of
+ * "update until the state is in an attractor, at most update_cap times" (pbn_target_multi.py:133-146) from every row.
+ * Columns [n_cols, ld) of d_out are not written. src: n_cols host doubles, NULL = all zero. The sum of a row is taken,
+ * per column, in pbn_stg_expect_device's order, fixed by N alone: the result is bit-identical from call to call, under
+ * any grid, and column c of a launch of several columns is bit-identical to the same column swept alone; with no
+ * labelled row, n_cols == 1 and src 0 it is pbn_stg_expect_device's (but -0.0 comes out +0.0: src is added). One launch on the device's default stream,
+ * asynchronous. A NULL handle or array, n_cols outside [1, PBN_STG_ABSORB_MAX_COLS], ld < n_cols, or d_out == d_x (a
+ * Jacobi sweep reads every row it has not yet written): PBN_E_INVALID; a host-only handle: PBN_E_STATE, decided after
+ * the argument checks. ---- */
+#define PBN_STG_ABSORB_MAX_COLS 8
+int pbn_stg_absorb_device(pbn_stg *g, const void *d_mass, const void *d_succ, const int32_t *d_label,
+                          const double *d_x, double *d_out, uint32_t n_cols, uint64_t ld, const double *src);
 
 #ifdef __cplusplus
 }
