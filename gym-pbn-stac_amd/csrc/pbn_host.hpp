@@ -452,6 +452,7 @@ struct pbn_stg {
         int bpc = 0;  // 0: not asked yet
     } ctl[CTL_KERNELS];
     Ctl absorb[4];  // k_stg_absorb (pbn_absorb.hip) for this graph's shape, by column tile 1, 2, 4, 8
+    Ctl flipset[2];  // k_stg_flipset for this graph's shape and k_stg_flipset_select (pbn_flipset.hip)
     uint32_t first_node() const { return net->L.kind == KIND_PROB_TABLE ? table_graph_first_node(graph) : 0u; }
     SetView view() const { return SetView{(const uint32_t*)meta.p, (const uint64_t*)keys.p, t.slots}; }
 };

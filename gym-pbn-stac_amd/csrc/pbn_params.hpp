@@ -522,8 +522,34 @@ struct StgAbsorbArgs {
     StgAbsorbSrc src;
 };
 
+// The max over multi-flip action sets (pbn_flipset.hip). A summary is base [S][2] float64 and tag [S][2]
+// int32 (pbn_flipset_rule.hpp: y | d << 24, -1 none), the better entry first.
+struct StgFlipsetArgs {
+    const int32_t* nbr;      // [S][N]: pbn_stg_flip_rows_device's array for the allowed nodes
+    const double* m;         // [S] the worth of arriving at a row: level 0 (in_base null), and the select
+    const double* in_base;   // [S][2] T_{j-1}, or null: T_0 is made from m
+    const int32_t* in_tag;   // [S][2]
+    double* out_base;        // [S][2] T_j, not in_base
+    int32_t* out_tag;        // [S][2]
+    double cost;             // k >= 0, per flip
+    uint64_t n_states;
+    uint32_t n_nodes;
+};
+
+struct StgFlipsetSelectArgs {
+    const double* base;      // [S][2] T_A
+    const int32_t* tag;      // [S][2]
+    const double* m;         // [S]
+    double cost, noop_cost;  // noop_cost is read where has_noop
+    uint32_t has_noop;
+    uint64_t n_states;
+    double* v;               // [S] the best action's value (-inf: none)
+    int32_t* policy_end;     // [S] the row it leads to (the row itself: the empty set; -1: none)
+    int32_t* policy_flips;   // [S] its flip count
+};
+
 // Launchers (pbn_step.hip, pbn_state.hip, pbn_env.hip, pbn_group.hip, pbn_mt.hip, pbn_ssd.hip, pbn_sync.hip, pbn_reach.hip,
-// pbn_tenv.hip, pbn_tenv_macro.hip, pbn_env_set.hip, pbn_stg.hip, pbn_control.hip, pbn_absorb.hip). Return hipError_t as int.
+// pbn_tenv.hip, pbn_tenv_macro.hip, pbn_env_set.hip, pbn_stg.hip, pbn_control.hip, pbn_absorb.hip, pbn_flipset.hip). Return hipError_t as int.
 // The lane-per-env kernels (pbn_lane_env.hpp): each file picks its kernel (nullptr: none for that shape), one
 // launcher and one occupancy query serve them all. plane_off: the LDS byte offset of the kernel's state planes;
 // args: the kernel's argument struct.
@@ -549,6 +575,10 @@ int max_blocks_control(void* kernel, int* blocks_per_cu);
 // pbn_absorb.hip: the kernel for AbsorbPlan's G, cells_per_lane == 1 and col_tile (nullptr: none for that shape); launched
 // and asked for occupancy through launch_control / max_blocks_control
 void* stg_absorb_kernel(uint32_t G, bool one_cell, uint32_t col_tile);
+// pbn_flipset.hip: the level kernel for ControlPlan's G and cells_per_lane == 1 (nullptr: none for that shape) and the
+// select kernel (a lane per row); launched and asked for occupancy through launch_control / max_blocks_control
+void* stg_flipset_kernel(uint32_t G, bool one_cell);
+void* stg_flipset_select_kernel();
 int launch_bump(uint64_t* p, uint64_t k, void* stream);
 int launch_set_counters(uint64_t* p, uint64_t v, uint32_t n, void* stream);
 int launch_step(int W, const StepArgs& a, int store_mode, int replay, int sb, int grid, void* stream);

@@ -55,6 +55,10 @@ def __getattr__(name):
         from . import absorption
 
         return getattr(absorption, name)
+    if name in ("MultiFlipProblem", "MultiFlipSolution", "host_multiflip_max", "host_multiflip_arrival"):
+        from . import multiflip
+
+        return getattr(multiflip, name)
     if name in ("TorchVecPBNEnv", "TorchVecPBNTargetMultiEnv", "TorchVecPBNTargetMultiSetEnv"):
         from . import torch_env
 

@@ -129,6 +129,7 @@ class StgInfo(C.Structure):
 STG_MAX_STATES = 1 << 24        # PBN_STG_MAX_STATES
 STG_MAX_CELLS = 1 << 31         # PBN_STG_MAX_CELLS: n_rows * n_nodes of one pbn_stg_rows_device call
 STG_ABSORB_MAX_COLS = 8         # PBN_STG_ABSORB_MAX_COLS: columns of one pbn_stg_absorb_device call
+STG_FLIPSET_MAX_FLIPS = 15      # PBN_STG_FLIPSET_MAX_FLIPS: levels that fit a summary's tag
 
 # pbn_tenv_macro_device: modes (PBN_MACRO_*) and the cap on t_max (PBN_TENV_MACRO_MAX_T)
 from .macro_env import MACRO_INTERVAL, MACRO_TRIGGER, TENV_MACRO_MAX_T  # noqa: E402,F401
@@ -230,6 +231,8 @@ SIGNATURES = {
     "pbn_stg_backup_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "pbn_stg_lookup_device": (C.c_int, [_vp, _vp, C.c_uint64, _vp]),
     "pbn_stg_absorb_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint64, C.POINTER(C.c_double)]),
+    "pbn_stg_flipset_level_device": (C.c_int, [_vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp]),
+    "pbn_stg_flipset_select_device": (C.c_int, [_vp, _vp, _vp, _vp, C.c_double, C.POINTER(C.c_double), _vp, _vp, _vp]),
 }
 
 

@@ -22,9 +22,8 @@ graph's law. If the next state is in the target the reward is ``R`` and the epis
 the set is not an action at that state.
 
 **Exact**: ``nbr`` and the action restriction the policy obeys (integers). **Float64**: every value and expectation.
-Memory: ``16 S N`` bytes for ``mass``, ``succ`` and ``nbr``. The until-attractor multi-flip MDP is not solved: the
-macro transition law of one of its steps is :mod:`gym_pbn_amd.absorption`, the max over multi-flip action sets is not
-built.
+Memory: ``16 S N`` bytes for ``mass``, ``succ`` and ``nbr``. The until-attractor multi-flip MDP is
+:mod:`gym_pbn_amd.multiflip`'s.
 """
 
 from __future__ import annotations

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define PBN_ABI_VERSION 25
+#define PBN_ABI_VERSION 26
 
 enum {
     PBN_OK = 0,
@@ -659,6 +659,30 @@ int pbn_stg_lookup_device(pbn_stg *g, const void *d_words, uint64_t n, int32_t *
 #define PBN_STG_ABSORB_MAX_COLS 8
 int pbn_stg_absorb_device(pbn_stg *g, const void *d_mass, const void *d_succ, const int32_t *d_label,
                           const double *d_x, double *d_out, uint32_t n_cols, uint64_t ld, const double *src);
+
+/* ---- The max over multi-flip action sets (csrc/pbn_flipset.hip, csrc/pbn_flipset_rule.hpp): the action
+ * of PBNTargetMultiEnv.step (pbn_target_multi.py:105-131) is a set F of 1 <= |F| <= A distinct allowed nodes, worth
+ * m[row of s ^ F] - cost * |F| with m [S] the worth of arriving at a row. d_nbr [S][N] int32 is what
+ * pbn_stg_flip_rows_device wrote for the allowed nodes over a set that is closed under those flips (-1 exactly on the
+ * nodes that are not allowed: the caller checks it; a cell that is no row adds nothing). A summary T_j is d_base [S][2]
+ * float64 and d_tag [S][2] int32, 16- and 8-byte aligned: the best two entries with distinct end rows among the ends
+ * within j flips of each row, the better first; tag = end row | flips << 24, -1 none; base = m[end]. The order: larger
+ * base - cost * flips (one multiply, one subtract, not contracted), then fewer flips, then the lower end row.
+ * Both calls are one launch on the device's default stream, asynchronous; results are bit-identical from call to call
+ * and under any grid. A NULL handle or array, a cost that is negative, NaN or infinite, or an output summary that
+ * aliases the input: PBN_E_INVALID; a host-only handle: PBN_E_STATE, decided after the argument checks. ---- */
+#define PBN_STG_FLIPSET_MAX_FLIPS 15
+/* T_j from T_{j-1}: d_out[s] = top-two-distinct of d_in[s] and, with one more flip, d_in[d_nbr[s][i]] for every i.
+ * d_in_base and d_in_tag NULL: level 0 -> 1, T_0[s] = (s, 0, d_m[s]) (d_m is not read otherwise and may be NULL then).
+ * At most PBN_STG_FLIPSET_MAX_FLIPS levels fit the tag. */
+int pbn_stg_flipset_level_device(pbn_stg *g, const void *d_nbr, const double *d_m, double cost, const double *d_in_base,
+                                 const int32_t *d_in_tag, double *d_out_base, int32_t *d_out_tag);
+/* The best action from T_A: the first entry whose end is not the row itself (the empty set is no action), so d_v[s] =
+ * its value, d_policy_end[s] its end row, d_policy_flips[s] its flip count; F = states[s] ^ states[policy_end[s]].
+ * noop_cost (a host double, NULL: none) makes the empty set an action worth d_m[s] - *noop_cost, taken on a tie:
+ * policy_end = s, policy_flips = 0. A row with no action at all: -inf, -1, 0. */
+int pbn_stg_flipset_select_device(pbn_stg *g, const double *d_base, const int32_t *d_tag, const double *d_m, double cost,
+                                  const double *noop_cost, double *d_v, int32_t *d_policy_end, int32_t *d_policy_flips);
 
 #ifdef __cplusplus
 }
